@@ -383,6 +383,49 @@ def extra_records(args, env, runner, obs_dict, device):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, args, runner, obs_dict, last):
+    """--dump-outputs: what the last timed step handed its caller, one DIR/<name>.npy each (float64 stays float64, all else float32).
+    The observations the rollout returns; unless --sim-only, the rollout in storage (actions, rewards, dones, values, log-probabilities)
+    with the returns and advantages computed from it; for the full step also the weights after the update (the flat fp32 master:
+    policy body then std) and the update's mean losses.  When the per-environment arrays would exceed DUMP_BUDGET_BYTES, a fixed
+    seeded sample of environments is kept (the same rows in every array); env_index.npy lists the environments kept.
+    The inputs are seeded and the update's cross-workgroup sums are taken in a fixed order (csrc/go1ppo.hip, det_last), so equal
+    arguments give the same arrays in every run."""
+    import numpy as np
+    per_env = {"obs": (obs_dict["obs"], 0), "privileged_obs": (obs_dict["privileged_obs"], 0), "obs_history": (obs_dict["obs_history"], 0)}
+    fixed = {}
+    if args.sim_only:
+        per_env.update(rewards=(last["rewards"], 0), dones=(last["dones"], 0))
+    else:
+        st = runner.alg.storage
+        for k in ("actions", "rewards", "dones", "values", "actions_log_prob", "returns", "advantages"):
+            per_env[k] = (getattr(st, k), 1)                               # (T, N, ...)
+        if not args.rollout_only:
+            alg = runner.alg
+            fixed["weights"] = alg.master[:alg.n_body + alg.n_std]
+            fixed["losses"] = torch.tensor(last["losses"], dtype=torch.float64)   # the eight mean losses PPO.update() returns
+    n_envs = obs_dict["obs"].shape[0]
+    size = lambda t: t.numel() * (8 if t.dtype == torch.float64 else 4)
+    row_bytes = 8 + sum(size(t) // t.shape[ax] for t, ax in per_env.values())          # (8: the row's env_index entry)
+    keep = min(n_envs, (DUMP_BUDGET_BYTES - (64 << 10) - sum(size(t) for t in fixed.values())) // row_bytes)   # (64 KB: .npy headers)
+    rows = np.arange(n_envs) if keep == n_envs else np.sort(np.random.default_rng(0).choice(n_envs, keep, replace=False))
+    idx = torch.from_numpy(rows).to(obs_dict["obs"].device)
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, t):
+        t = t.detach()
+        t = t if t.dtype == torch.float64 else t.float()
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy())
+    for name, (t, ax) in per_env.items():
+        save(name, t if keep == n_envs else t.index_select(ax, idx.to(t.device)))
+    for name, t in fixed.items():
+        save(name, t)
+    save("env_index", torch.from_numpy(rows.astype(np.float64)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -409,7 +452,12 @@ def main():
                     help="commands.curriculum_update_interval K: 1 = the reference's per-step curriculum update (curriculum.py) at EVERY rank count, so "
                          "that the 1-GPU headline and the N-GPU scaling numbers run the same algorithm; K > 1 coalesces the sharded run's "
                          "success-count all-reduce to one per K steps (samples inside the window see the weights from its start)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most "
+                         f"{DUMP_BUDGET_BYTES >> 20} MB; rank 0): observations handed back, the rollout, returns / advantages, updated weights, losses")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -482,6 +530,7 @@ def main():
     runner.alg.actor_critic.train()
 
     split = {"rollout": 0.0, "update": 0.0}
+    last = {}                                   # what the last iteration returned beside obs_dict (the update's losses, the env's last step)
 
     def iteration(obs_dict):
         if args.breakdown:
@@ -498,7 +547,7 @@ def main():
         if args.rollout_only:
             runner.alg.storage.clear()
             return obs_dict
-        runner.alg.update()
+        last["losses"] = runner.alg.update()
         if args.breakdown:
             torch.cuda.synchronize()
             split["rollout"] += tb - ta
@@ -507,7 +556,7 @@ def main():
 
     def sim_iteration(obs_dict, acts):
         for t in range(T):
-            obs_dict, _, _, _ = env.step(acts[t])
+            obs_dict, last["rewards"], last["dones"], _ = env.step(acts[t])
         return obs_dict
 
     def barrier():
@@ -529,6 +578,8 @@ def main():
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t)
+    if args.dump_outputs and rank == 0:         # before anything below steps the environment or the policy again
+        dump_outputs(args.dump_outputs, args, runner, obs_dict, last)
 
     kernel_ms = sim.read_timings()
     if dp_trace is not None and rank == 0:

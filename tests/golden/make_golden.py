@@ -1318,3 +1318,4 @@ if __name__ == "__main__":
     import subprocess
     subprocess.check_call([sys.executable, os.path.join(HERE, "gen_runner_iteration.py")])      # (its own interpreter: two go1_gym_learn packages)
     subprocess.check_call([sys.executable, os.path.join(HERE, "gen_runner_iteration.py"), "eval"])
+    subprocess.check_call([sys.executable, os.path.join(HERE, "gen_reference_scripts.py")])     # (this repository's go1_gym under the reference's scripts)

@@ -1,56 +1,38 @@
-"""The reference's scripts/train.py must run unchanged on top of this package's modules.
+"""The reference's scripts/train.py must configure this package's environment exactly as bench.py / smoke() do.
 
-Executed here (authoring container, where /root/reference exists): the reference script's `train_go1` is run
-verbatim with our `go1_gym`, `go1_gym_learn`, `params_proto`/`ml_logger`/`isaacgym` stand-ins on sys.path; the
-env constructor is intercepted (no GPU here) and the `Cfg` it would have been built from is compared with the
-table bench.py / smoke() use (walk-these-ways_amd/scripts/train_config.py).  Skipped where the reference tree is
-absent (GPU box)."""
-import importlib.util
+The reference script's `train_go1` was run verbatim over this repository's `go1_gym`, `go1_gym_learn`, `params_proto`/`ml_logger`/`isaacgym`
+stand-ins, with the env constructor intercepted; the `Cfg` it would have been built from is stored in tests/golden/reference_train_cfg.json
+(tests/golden/gen_reference_scripts.py) and compared here with the table bench.py / smoke() use
+(walk-these-ways_amd/scripts/train_config.py)."""
+import hashlib
+import json
 import os
-import sys
 
 import pytest
 
-REF_TRAIN = "/root/reference/scripts/train.py"
+
+def _golden(name):
+    from util import GOLDEN
+    return os.path.join(GOLDEN, name)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_TRAIN), reason="reference tree not present")
-def test_reference_train_script_configures_our_env(monkeypatch):
-    import go1_gym.envs.go1.velocity_tracking as vt
+def test_reference_train_script_configures_our_env():
     import go1_gym_learn.ppo_cse as runner_mod
-    from go1_gym.envs.base import legged_robot_config
     from go1_gym.envs.base.legged_robot_config import make_cfg
     from scripts.train_config import apply_train_config
     import go1sim_host as H
-    from ml_logger import logger
 
-    fresh = make_cfg()
-    monkeypatch.setattr(legged_robot_config, "Cfg", fresh)
-    captured = {}
-
-    class FakeEnv:
-        def __init__(self, sim_device, headless, cfg=None, **kw):
-            captured.update(sim_device=sim_device, cfg=cfg)
-            raise StopIteration           # stop train_go1 right after the env would have been constructed
-
-    monkeypatch.setattr(vt, "VelocityTrackingEasyEnv", FakeEnv)
-    spec = importlib.util.spec_from_file_location("ref_train", REF_TRAIN)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)          # imports only; __main__ block does not run
-    logger.configure("test", root="/tmp/wtw_logger_test")
-    with pytest.raises(StopIteration):
-        mod.train_go1(headless=True)
-    assert captured["sim_device"] == "cuda:0"
-    ref_cfg = captured["cfg"]
+    with open(_golden("reference_train_cfg.json")) as f:
+        ref = json.load(f)
+    assert ref["sim_device"] == "cuda:0"
     ours = apply_train_config(make_cfg())
-    assert vars(ref_cfg) == vars(ours)
+    assert json.loads(json.dumps(vars(ours))) == ref["cfg"]
     # and the flattened simulator configuration is byte-identical
-    S1, m1 = H.build_sim_config(ref_cfg, num_envs=64)
-    S2, m2 = H.build_sim_config(ours, num_envs=64)
-    assert bytes(S1) == bytes(S2)
-    assert m1["reward_names"] == m2["reward_names"] and len(m1["reward_names"]) == 19
-    assert (S1.max_episode_length, S1.resample_interval, S1.rand_interval, S1.gravity_rand_interval,
-            S1.gravity_rand_duration) == (1001, 500, 201, 401, 397)
+    S, m = H.build_sim_config(ours, num_envs=64)
+    assert hashlib.sha256(bytes(S)).hexdigest() == ref["sim_config_sha256_64_envs"]
+    assert m["reward_names"] == ref["reward_names"] and len(m["reward_names"]) == 19
+    assert (S.max_episode_length, S.resample_interval, S.rand_interval, S.gravity_rand_interval,
+            S.gravity_rand_duration) == (1001, 500, 201, 401, 397)
     assert hasattr(runner_mod, "Runner") and hasattr(runner_mod, "RunnerArgs")
 
 
@@ -63,131 +45,47 @@ def test_cpu_device_is_refused_loudly():
         VelocityTrackingEasyEnv(sim_device="cpu", headless=True, cfg=cfg)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_TRAIN), reason="reference tree not present")
-def test_reference_train_script_runs_one_iteration_end_to_end(monkeypatch, tmp_path):
-    """The reference's `train_go1` body, verbatim, THROUGH the constructor and into `Runner(env).learn(...)`
-    (train.py:207-216): env construction, HistoryWrapper, logger.log_params / log_text, Runner with RunnerArgs,
-    one full PPO iteration (rollout, GAE, update, metrics, checkpoint + TorchScript export).  No GPU in this container:
-    the simulator handle is the oracle-backed stand-in (tests/fake_sim.py) on CPU buffers, the env is shrunk to 48
-    robots and the Runner is pointed at 'cpu'; every class in between is the product's.  Then the reference's scripts/play.py
-    on the run directory this produced: `load_policy` on the exported TorchScript files and `play_go1` verbatim (configuration
-    read back from the logged parameters.pkl, one environment, 250 policy steps)."""
-    import fake_sim
-    import go1_gym.envs.go1.velocity_tracking as vt
-    import go1_gym_learn.ppo_cse as runner_mod
-    from go1_gym.envs.base import legged_robot_config
-    from go1_gym.envs.base.legged_robot_config import make_cfg
-    from ml_logger import logger
-
-    monkeypatch.setattr(legged_robot_config, "Cfg", make_cfg())
-    fake_sim.install(monkeypatch)
-    real_env, real_runner = vt.VelocityTrackingEasyEnv, runner_mod.Runner
-    seen = {}
-
-    def small_env(sim_device, headless, cfg=None, **kw):
-        seen["sim_device"] = sim_device
-        return real_env(sim_device, headless, num_envs=48, cfg=cfg, **kw)
-
-    class CpuRunner(real_runner):
-        def __init__(self, env, device="cpu"):
-            seen["runner_device"] = device
-            super().__init__(env, device="cpu")
-
-        def learn(self, num_learning_iterations, **kw):
-            seen["learn_kwargs"] = dict(num_learning_iterations=num_learning_iterations, **kw)
-            return super().learn(1, **kw)
-
-    monkeypatch.setattr(vt, "VelocityTrackingEasyEnv", small_env)
-    monkeypatch.setattr(runner_mod, "Runner", CpuRunner)
-    spec = importlib.util.spec_from_file_location("ref_train_full", REF_TRAIN)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    logger.configure("dropin", root=str(tmp_path))
-    logger.print_summary = False
-    monkeypatch.chdir(tmp_path)
-    old = (runner_mod.RunnerArgs.save_video_interval,)
-    try:
-        mod.train_go1(headless=True)
-    finally:
-        (runner_mod.RunnerArgs.save_video_interval,) = old
-    assert seen["sim_device"] == "cuda:0" and seen["runner_device"] == "cuda:0"
-    assert seen["learn_kwargs"] == dict(num_learning_iterations=100000, init_at_random_ep_len=True, eval_freq=100)   # train.py:216
-    ck = tmp_path / "dropin" / "checkpoints"
-    assert (ck / "ac_weights_last.pt").exists() and (ck / "adaptation_module_latest.jit").exists() and (ck / "body_latest.jit").exists()
-    from util import check_exported_policy_layout
-    check_exported_policy_layout(str(ck))
-    # ... and the reference's own play.py loader (`load_policy`, play.py:17-29) turns that run directory into a policy
-    import torch
-    spec = importlib.util.spec_from_file_location("ref_play", "/root/reference/scripts/play.py")
-    play = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(play)
-    policy = play.load_policy(str(tmp_path / "dropin"))
-    info = {}
-    act = policy({"obs_history": torch.randn(5, 2100)}, info)
-    assert act.shape == (5, 12) and info["latent"].shape == (5, 2) and bool(torch.isfinite(act).all())
-    # ... the REFERENCE ActorCritic loads the weights file strictly (its own interpreter: the package names collide)
-    import subprocess
-    code = ("import sys, torch; sys.path[:0] = [%r, '/root/reference']; "
-            "from go1_gym_learn.ppo_cse.actor_critic import ActorCritic; import go1_gym_learn; "
-            "assert go1_gym_learn.__file__.startswith('/root/reference'); ac = ActorCritic(70, 2, 2100, 12); "
-            "r = ac.load_state_dict(torch.load(%r, map_location='cpu'), strict=True); print('LOADED', r)"
-            % (os.path.join(os.path.dirname(__file__), "..", "walk-these-ways_amd", "shims"), str(ck / "ac_weights_last.pt")))
-    res = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert "LOADED <All keys matched successfully>" in res.stdout, res.stdout[-500:] + res.stderr[-1500:]
-    # ... and `play_go1` verbatim (play.py:89-157): the run directory found by its glob, `parameters.pkl` as train.py logged it
-    # read back into Cfg, one environment, the policy in the loop for 250 steps, the two plots (Agg backend)
-    import matplotlib
-    matplotlib.use("Agg")
-    run = tmp_path / "runs" / "gait-conditioned-agility" / "pretrain-v0" / "train"
-    run.mkdir(parents=True)
-    os.symlink(tmp_path / "dropin", run / "000000.000000")
-    (tmp_path / "scripts").mkdir()
-    monkeypatch.chdir(tmp_path / "scripts")
-    monkeypatch.setattr(vt, "VelocityTrackingEasyEnv", real_env)           # (play.py builds its single environment itself)
-    monkeypatch.setattr(play, "VelocityTrackingEasyEnv", real_env)
-    monkeypatch.setattr(play, "tqdm", lambda it: it)
-    fresh = make_cfg()                                                     # (play.py runs in its own process: a pristine Cfg)
-    monkeypatch.setattr(legged_robot_config, "Cfg", fresh)
-    monkeypatch.setattr(play, "Cfg", fresh)
-    play.play_go1(headless=True)
-    monkeypatch.chdir(tmp_path)
-    metrics = logger.load_pkl("metrics.pkl")
-    assert metrics and metrics[-1]["timesteps"] == 24 * 48
-    assert any(k.startswith("train/episode/rew_") for k in metrics[-1])
-
-
-REF_TEST = "/root/reference/scripts/test.py"
-
-
-@pytest.mark.skipif(not os.path.exists(REF_TEST), reason="reference tree not present")
-def test_reference_test_script_runs_verbatim(monkeypatch):
-    """BASELINE configs[0] semantics: the reference's scripts/test.py `run_env` verbatim — config, env construction,
-    `env.reset()`, 1000 steps of zero actions with the 4-tuple return (test.py:188-200) — on the oracle-backed stand-in."""
+def test_reference_test_script_configuration_runs_on_this_environment(monkeypatch):
+    """BASELINE configs[0] semantics: the `Cfg` the reference's scripts/test.py `run_env` builds (tests/golden/reference_test_cfg.json,
+    recorded by gen_reference_scripts.py), this package's environment constructed from it on the oracle-backed stand-in, `env.reset()`,
+    then 1000 steps of zero actions with the 4-tuple return (test.py:188-200)."""
     import fake_sim
     import torch
-    import go1_gym.envs.go1.velocity_tracking as vt
     from go1_gym.envs.base import legged_robot_config
     from go1_gym.envs.base.legged_robot_config import make_cfg
+    from go1_gym.envs.go1.velocity_tracking import VelocityTrackingEasyEnv
 
-    monkeypatch.setattr(legged_robot_config, "Cfg", make_cfg())
+    with open(_golden("reference_test_cfg.json")) as f:
+        ref = json.load(f)
+    assert ref["sim_device"] == "cuda:0"                                  # (what test.py asks for: the GPU simulator)
+    cfg = make_cfg()
+    for section, values in ref["cfg"].items():
+        for k, v in values.items():
+            setattr(getattr(cfg, section), k, v)
+    assert json.loads(json.dumps(vars(cfg))) == ref["cfg"]
+    monkeypatch.setattr(legged_robot_config, "Cfg", cfg)
     fake_sim.install(monkeypatch)
-    made = []
-    real_env = vt.VelocityTrackingEasyEnv
-
-    def env_factory(*a, **kw):
-        made.append(real_env(*a, **kw))
-        return made[-1]
-    monkeypatch.setattr(vt, "VelocityTrackingEasyEnv", env_factory)
-    spec = importlib.util.spec_from_file_location("ref_test_script", REF_TEST)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    mod.run_env(render=False, headless=True)
-    env = made[0]
+    env = VelocityTrackingEasyEnv(sim_device=ref["sim_device"], headless=True, cfg=cfg)
+    env.reset()
+    for _ in range(1000):
+        out = env.step(0. * torch.ones(env.num_envs, env.num_actions, device=env.device))
+        assert len(out) == 4
     assert env.num_envs == 3 and env.common_step_counter == 1001          # reset()'s step + 1000
     assert env.obs_buf.shape == (3, env.num_obs) and env.obs_buf.dtype == torch.float32
     for t in (env.obs_buf, env.rew_buf, env.root_states, env.dof_pos, env.contact_forces):
         assert torch.isfinite(t).all()
     assert float(env.root_states[:, 2].min()) > 0.15                      # zero actions: the robots stand
+
+
+def test_weights_file_layout_equals_the_reference_actor_critic():
+    """The weights file the Runner saves (`ActorCritic.state_dict()`) must load STRICTLY into the reference's own ActorCritic (scripts/
+    play.py, the deployment stack): same parameter names and shapes as the reference's ActorCritic(70, 2, 2100, 12)
+    (tests/golden/reference_actor_critic.json, recorded by gen_reference_scripts.py)."""
+    from go1_gym_learn.ppo_cse.actor_critic import ActorCritic
+    with open(_golden("reference_actor_critic.json")) as f:
+        ref = json.load(f)
+    mine = {k: list(v.shape) for k, v in ActorCritic(70, 2, 2100, 12).state_dict().items()}
+    assert mine == ref
 
 
 def test_every_reference_module_path_on_the_hot_path_resolves():
@@ -326,46 +224,32 @@ def test_runner_reproduces_the_reference_runner_end_to_end(monkeypatch, tmp_path
         np.testing.assert_allclose(v.numpy(), d["final_" + k], rtol=1e-3, atol=1e-4, err_msg=k)
 
 
-REF_WRAPPER = "/root/reference/go1_gym/envs/wrappers/history_wrapper.py"
-
-
-@pytest.mark.skipif(not os.path.exists(REF_WRAPPER), reason="reference tree not present")
 def test_reference_history_wrapper_over_this_environment(monkeypatch):
     """The REFERENCE `HistoryWrapper` class (history_wrapper.py:6-41, `torch.cat` of the history every call) wrapped around this
-    repository's environment, next to the product's wrapper (a window of the ring the simulator appends to) around an identical
-    second environment: same observation dicts call by call — reset, the extra shift of get_observations, steps across episode
-    ends (the history is not cleared when an environment resets)."""
+    repository's environment (tests/golden/reference_history_wrapper.npz, gen_reference_scripts.py), against the product's wrapper (a
+    window of the ring the simulator appends to) around an identical environment: same observation dicts call by call — reset, the
+    extra shift of get_observations, steps across episode ends (the history is not cleared when an environment resets)."""
     import numpy as np
-    import torch
     import fake_sim
-    from go1_gym.envs.base.legged_robot_config import make_cfg
-    from go1_gym.envs.go1.velocity_tracking import VelocityTrackingEasyEnv
+    from golden import gen_reference_scripts as G
     from go1_gym.envs.wrappers.history_wrapper import HistoryWrapper
-    from scripts.train_config import apply_train_config
+    d = np.load(_golden("reference_history_wrapper.npz"))
+    assert [str(c) for c in d["calls"]] == G.HISTORY_CALLS
     fake_sim.install(monkeypatch)
-    spec = importlib.util.spec_from_file_location("_ref_history_wrapper", REF_WRAPPER)
-    ref_mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref_mod)
-
-    def build():
-        cfg = apply_train_config(make_cfg(), num_envs=16)
-        cfg.terrain.mesh_type = "plane"
-        cfg.env.episode_length_s = 0.2                 # episodes end inside the run
-        cfg.env.num_observation_history = 5
-        torch.manual_seed(0)
-        return VelocityTrackingEasyEnv(sim_device="cuda:0", headless=True, cfg=cfg)
-    mine, ref = HistoryWrapper(build()), ref_mod.HistoryWrapper(build())
-    assert (mine.num_obs_history, mine.obs_history_length) == (ref.num_obs_history, ref.obs_history_length) == (350, 5)
-    g = torch.Generator().manual_seed(1)
-    resets = 0
-    for call in ["reset", "get_observations"] + ["step"] * 7 + ["get_observations"] + ["step"] * 9 + ["reset", "step", "step"]:
+    mine = HistoryWrapper(G.build_history_env())
+    assert (mine.num_obs_history, mine.obs_history_length) == (d["obs_history"].shape[-1], 5) == (350, 5)
+    acts = iter(G.history_actions())
+    resets, k = 0, 0
+    for i, call in enumerate(G.HISTORY_CALLS):
         if call == "step":
-            a = 0.5 * torch.randn(16, 12, generator=g)
-            (om, rm, dm, _), (orf, rr, dr, _) = mine.step(a.clone()), ref.step(a.clone())
-            assert torch.equal(rm, rr) and torch.equal(dm, dr)
+            om, rm, dm, _ = mine.step(next(acts))
+            np.testing.assert_array_equal(dm.numpy(), d["dones"][k])
+            np.testing.assert_allclose(rm.numpy(), d["rewards"][k], rtol=1e-6, atol=1e-6)
             resets += int(dm.sum())
+            k += 1
         else:
-            om, orf = getattr(mine, call)(), getattr(ref, call)()
-        for k in ("obs", "privileged_obs", "obs_history"):
-            assert torch.equal(om[k], orf[k]), (call, k, float((om[k] - orf[k]).abs().max()))
+            om = getattr(mine, call)()
+        for key in ("obs", "privileged_obs", "obs_history"):
+            # (stored on one machine, replayed on another: the oracle's round-off may differ in the last bits, a misplaced slot does not)
+            np.testing.assert_allclose(om[key].numpy(), d[key][i], rtol=1e-6, atol=1e-6, err_msg=f"{call} #{i}: {key}")
     assert resets > 0

@@ -910,6 +910,28 @@ def test_fused_graph_replay_equals_eager_at_production_size():
         assert b[u][2] == pytest.approx(a[u][2], rel=1e-5)
 
 
+def test_fused_update_is_bit_reproducible_at_production_size():
+    """Two runs of the product update (HIP graphs, bf16, 4096 envs x 24 steps, three updates) from the same seeds give the same bytes:
+    weights, gradients, losses and learning rate.  The update's cross-workgroup sums (loss and MSE kernels, GAE statistics, the batched
+    weight-gradient kernel's bias columns) are taken in a fixed order (csrc/go1ppo.hip, det_last) and the weight gradients go through
+    slabs, so nothing depends on the order in which workgroups finish."""
+    import os
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(repo, "tools", "debug"))
+    import graph_vs_eager as G
+    from go1_gym_learn.ppo_cse.ppo import PPO_Args
+    try:
+        a = G.run(True, True, 3, 4096, 24, True, fused=True)
+        b = G.run(True, True, 3, 4096, 24, True, fused=True)
+    finally:
+        PPO_Args.autocast_bf16, PPO_Args.use_fused_kernels, PPO_Args.use_hip_graphs = False, True, True
+    for u in range(3):
+        assert torch.equal(a[u][0], b[u][0]), (u, float((a[u][0] - b[u][0]).abs().max()))
+        assert torch.equal(a[u][3], b[u][3]), (u, float((a[u][3] - b[u][3]).abs().max()))
+        assert list(a[u][1]) == list(b[u][1]) and a[u][2] == b[u][2], (u, a[u][1], b[u][1])
+
+
 def test_observation_ring_storage_is_bit_identical_to_the_history_block():
     """RolloutStorage(ring=True) — every observation stored once, (T + H - 1, N, 70) bf16 — against the reference layout
     (rollout_storage.py:36-38: every window stored, here (T, N, 2112) bf16): same sliding-window input stream

@@ -183,9 +183,47 @@ __global__ __launch_bounds__(256) void elu_bwd_tile_kernel(const bf16_t* d, int 
   }
 }
 
+// ---------------------------------------------------------------------------------------------- fixed-order cross-workgroup sums
+// The sums that many workgroups contribute to (loss and loss gradients, bias gradients, the advantage statistics) are not met in
+// fp32 atomics: their order, and so their rounding, would change from run to run, and the training that follows would drift apart.
+// Every contributing workgroup STORES its partial values as its own row of a slab (static device buffers below, one per call site);
+// the last contributor to arrive (counted on an integer counter) adds the column sums, taken in row order, to the destinations and
+// resets the counter for the next launch.  Launches of one site follow each other on a stream, so a site's slab is never shared.
+#define DET_MAX_BLOCKS 4096                                       // loss / MSE / GAE workgroups per launch (rows <= 1 M)
+#define DET_LOSS_W (4 + 2 * GO1PPO_MAX_ACTIONS)
+#define GO1PPO_HEAD 64                                            // padded head width of the policy (fused.py HEAD): npv <= 64
+#define DET_MSE_W (GO1PPO_HEAD + 2)                               // bias-gradient columns + train and test loss
+#define DET_TN_MAXP 16                                            // weight-gradient problems with a bias per batched launch
+#define DET_TN_MAXNT 4                                            // n tiles per problem (n <= 512)
+#define DET_TN_MAXS 512                                           // row chunks per problem
+#define DET_TN_W 256                                              // bias values per n tile (the 256-wide tile)
+__device__ float det_loss_slab[DET_MAX_BLOCKS * DET_LOSS_W];
+__device__ float det_mse_slab[DET_MAX_BLOCKS * DET_MSE_W];
+__device__ double det_gae_slab[DET_MAX_BLOCKS * 2];
+__device__ float det_tn_slab[DET_TN_MAXP * DET_TN_MAXNT * DET_TN_MAXS * DET_TN_W];
+__device__ unsigned det_count[3 + DET_TN_MAXP * DET_TN_MAXNT];  // [0] loss, [1] MSE, [2] GAE, [3 + p * MAXNT + tile] TN bias
+enum { DET_LOSS = 0, DET_MSE = 1, DET_GAE = 2, DET_TN = 3 };
+
+// after this workgroup's slab stores: true in the last of `parts` contributors (all of whose stores it then sees)
+__device__ __forceinline__ bool det_last(unsigned* counter, unsigned parts) {
+  __shared__ unsigned s_last;
+  __threadfence();                                               // release: this workgroup's slab row, device-wide
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned t = atomicAdd(counter, 1u);
+    s_last = t == parts - 1;
+    if (s_last) atomicExch(counter, 0u);                         // every contributor has counted: ready for the next launch
+  }
+  __syncthreads();
+  const bool last = s_last;
+  if (last) __threadfence();                                     // acquire: the other rows
+  return last;
+}
+
 // ---------------------------------------------------------------------------------------------- block reduction helper
+// the workgroup's sums of v[i] are STORED to dst[i] (a slab row; null: not needed)
 template <int NV>
-__device__ __forceinline__ void block_reduce_atomic(float (&v)[NV], float* const (&dst)[NV], float* lds /* [4][NV] */) {
+__device__ __forceinline__ void block_reduce_store(float (&v)[NV], float* const (&dst)[NV], float* lds /* [4][NV] */) {
 #pragma unroll
   for (int i = 0; i < NV; i++) {
     float x = v[i];
@@ -201,9 +239,9 @@ __device__ __forceinline__ void block_reduce_atomic(float (&v)[NV], float* const
     float t = 0.f;
     for (int w = 0; w < (int)(blockDim.x >> 6); w++) t += lds[w * NV + threadIdx.x];
 #if defined(LOSS_ABLATE) && (LOSS_ABLATE & 8)
-    if (dst[threadIdx.x] && t == 12345.678f) *dst[threadIdx.x] = t;      // probe build: the reduction without its atomics
+    if (dst[threadIdx.x] && t == 12345.678f) *dst[threadIdx.x] = t;      // probe build: the reduction without its cross-workgroup sums
 #else
-    if (dst[threadIdx.x]) atomicAdd(dst[threadIdx.x], t);
+    if (dst[threadIdx.x]) *dst[threadIdx.x] = t;
 #endif
   }
 }
@@ -344,11 +382,12 @@ __global__ __launch_bounds__(256) void loss_kernel(Go1PpoLossArgs a) {
   float sur, vl, kl, dvb;
   float dstd[GO1PPO_MAX_ACTIONS], dmb[GO1PPO_MAX_ACTIONS];
   loss_sample(a, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, sur, vl, kl, dvb, dstd, dmb);
-  // reductions: [sur, vl, kl, dvb] then dstd[A], dmb[A]
+  // reductions: [sur, vl, kl, dvb] then dstd[A], dmb[A] — slab row blockIdx.x, columns in that order
+  float* row = det_loss_slab + (int64_t)blockIdx.x * DET_LOSS_W;
   {
     float v4[4] = {sur, vl, kl, dvb};
-    float* const d4[4] = {a.surrogate_loss, a.value_loss, a.kl, a.d_value_bias};
-    block_reduce_atomic<4>(v4, d4, lds);
+    float* const d4[4] = {row, row + 1, row + 2, row + 3};
+    block_reduce_store<4>(v4, d4, lds);
   }
   __syncthreads();
 #pragma unroll
@@ -361,16 +400,30 @@ __global__ __launch_bounds__(256) void loss_kernel(Go1PpoLossArgs a) {
         bool ok = j0 + q < A;
         v8[q] = ok ? dstd[j0 + q] : 0.f;
         v8[4 + q] = ok ? dmb[j0 + q] : 0.f;
-        d8[q] = ok ? a.d_std + j0 + q : nullptr;
-        d8[4 + q] = ok ? a.d_mean_bias + j0 + q : nullptr;
+        d8[q] = ok ? row + 4 + j0 + q : nullptr;
+        d8[4 + q] = ok ? row + 4 + A + j0 + q : nullptr;
       }
       float* const d8c[8] = {d8[0], d8[1], d8[2], d8[3], d8[4], d8[5], d8[6], d8[7]};
-      block_reduce_atomic<8>(v8, d8c, lds);
+      block_reduce_store<8>(v8, d8c, lds);
       __syncthreads();
     }
   }
-  // entropy term: loss -= entropy_coef * (sum log sigma + const)  ->  d/d sigma_j = -entropy_coef / sigma_j  (once)
-  if (blockIdx.x == 0 && threadIdx.x < A) atomicAdd(a.d_std + threadIdx.x, -a.entropy_coef / a.std[threadIdx.x]);
+#if defined(LOSS_ABLATE) && (LOSS_ABLATE & 8)
+  return;                                                                 // probe build: no cross-workgroup sums
+#endif
+  if (!det_last(&det_count[DET_LOSS], gridDim.x)) return;
+  for (int c = threadIdx.x; c < 4 + 2 * A; c += blockDim.x) {
+    float t = 0.f;
+#pragma unroll 16
+    for (unsigned b = 0; b < gridDim.x; b++) t += det_loss_slab[(int64_t)b * DET_LOSS_W + c];
+    float* dst = c < 4 ? (c == 0 ? a.surrogate_loss : c == 1 ? a.value_loss : c == 2 ? a.kl : a.d_value_bias)
+                       : c < 4 + A ? a.d_std + (c - 4) : a.d_mean_bias + (c - 4 - A);
+    if (!dst) continue;
+    float s = *dst + t;
+    // entropy term: loss -= entropy_coef * (sum log sigma + const)  ->  d/d sigma_j = -entropy_coef / sigma_j  (once)
+    if (c >= 4 && c < 4 + A) s += -a.entropy_coef / a.std[c - 4];
+    *dst = s;
+  }
 }
 
 // ---------------------------------------------------------------------------------------------- adaptation MSE
@@ -403,16 +456,26 @@ __global__ __launch_bounds__(256) void mse_kernel(const bf16_t* pred, int pred_l
     bool last = j0 + 6 >= ncol;
     v8[6] = last ? ltrain : 0.f;
     v8[7] = last ? ltest : 0.f;
+    // slab row blockIdx.x: bias-gradient columns 0..ncol-1, then the train and test losses
+    float* row = det_mse_slab + (int64_t)blockIdx.x * DET_MSE_W;
     float* d8[8];
-    for (int q = 0; q < 6; q++) d8[q] = (j0 + q < ncol) ? d_pred_bias + j0 + q : nullptr;
-    d8[6] = last ? train_loss : nullptr;
-    d8[7] = last ? test_loss : nullptr;
+    for (int q = 0; q < 6; q++) d8[q] = (j0 + q < ncol) ? row + j0 + q : nullptr;
+    d8[6] = last ? row + ncol : nullptr;
+    d8[7] = last ? row + ncol + 1 : nullptr;
     float* const d8c[8] = {d8[0], d8[1], d8[2], d8[3], d8[4], d8[5], d8[6], d8[7]};
-    block_reduce_atomic<8>(v8, d8c, lds);
+    block_reduce_store<8>(v8, d8c, lds);
     __syncthreads();
   }
   if (selective && r < rows)      // columns the selective loss ignores carry no gradient
     for (int j = 1; j < npv; j++) d_pred[r * pred_ld + j] = 0;
+  if (!det_last(&det_count[DET_MSE], gridDim.x)) return;
+  for (int c = threadIdx.x; c < ncol + 2; c += blockDim.x) {
+    float t = 0.f;
+#pragma unroll 16
+    for (unsigned b = 0; b < gridDim.x; b++) t += det_mse_slab[(int64_t)b * DET_MSE_W + c];
+    float* dst = c < ncol ? d_pred_bias + c : c == ncol ? train_loss : test_loss;
+    if (dst) *dst += t;
+  }
 }
 
 // ---------------------------------------------------------------------------------------------- wgrad (MFMA, split rows)
@@ -590,7 +653,14 @@ __global__ __launch_bounds__(256) void gae_kernel(const float* rewards, const ui
   for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); }
   if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s1; red[1][threadIdx.x >> 6] = s2; }
   __syncthreads();
-  if (threadIdx.x < 2) atomicAdd(stats + threadIdx.x, red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3]);
+  if (threadIdx.x < 2) det_gae_slab[(int64_t)blockIdx.x * 2 + threadIdx.x] = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+  if (!det_last(&det_count[DET_GAE], gridDim.x)) return;
+  if (threadIdx.x < 2) {
+    double t = 0.0;
+#pragma unroll 16
+    for (unsigned b = 0; b < gridDim.x; b++) t += det_gae_slab[(int64_t)b * 2 + threadIdx.x];
+    stats[threadIdx.x] += t;
+  }
 }
 
 // advantages = (advantages - mean) / (std + 1e-8), unbiased std from stats = [sum, sum of squares, count]
@@ -1063,10 +1133,13 @@ extern "C" int go1ppo_elu_bwd(const void* d, int ld_d, const void* h, int ld_h, 
 
 extern "C" int go1ppo_loss(const Go1PpoLossArgs* a, void* stream) {
   if (!a || a->rows <= 0 || a->num_actions <= 0 || a->num_actions > GO1PPO_MAX_ACTIONS || a->head_ld < a->num_actions) return -1;
+  if ((a->rows + 255) / 256 > DET_MAX_BLOCKS) return -1;                 // one row of det_loss_slab per workgroup
   // (measured: 64-thread workgroups — 384 instead of 96 — are slower, 33 vs 26 us: four times the atomics on the same 28 words)
   // (one wavefront per workgroup — 384 workgroups instead of 96 — measured 32 us against 22: four times the same-address atomics of the reductions)
   // (measured, round 6 — profiles/r06_loss_kernel_ablation.txt: the same-address atomics are 1 us of the kernel's 16-22; meeting the sums through
-  //  per-workgroup rows and a last-workgroup ticket instead took 45 us: the device-scope fences in front of the ticket write the XCD's L2 back)
+  //  per-workgroup rows and a last-workgroup ticket instead took 45 us: the device-scope fences in front of the ticket write the XCD's L2 back.
+  //  That is the form the kernel now has (det_last): the price of sums that come out the same in every run; fp32 atomics made the update —
+  //  and so every later rollout — differ from run to run.  Its cost in the update: profiles/det_sums_kernel_stats.txt)
   loss_kernel<<<dim3((unsigned)((a->rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(*a);
   return hipGetLastError() == hipSuccess ? 0 : -9;
 }
@@ -1074,6 +1147,7 @@ extern "C" int go1ppo_mse(const void* pred, int pred_ld, const float* target, in
                           int64_t num_train, int selective, void* d_pred, float* d_pred_bias, float* train_loss,
                           float* test_loss, void* stream) {
   if (!pred || !target || !idx || rows <= 0 || num_train <= 0 || num_train >= rows || npv <= 0 || npv > pred_ld) return -1;
+  if (npv > GO1PPO_HEAD || (rows + 255) / 256 > DET_MAX_BLOCKS) return -1;   // one row of det_mse_slab (npv + 2 columns) per workgroup
   mse_kernel<<<dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(
       (const bf16_t*)pred, pred_ld, target, npv, idx, rows, num_train, selective, (bf16_t*)d_pred, d_pred_bias, train_loss, test_loss);
   return hipGetLastError() == hipSuccess ? 0 : -9;
@@ -1118,6 +1192,7 @@ extern "C" int go1ppo_store_step(const float* rewards, const uint8_t* dones, con
 extern "C" int go1ppo_gae(const float* rewards, const uint8_t* dones, const float* values, const float* last_values, int T, int64_t N,
                           float gamma, float lam, float* returns, float* advantages, double* stats, void* stream) {
   if (!rewards || !dones || !values || !last_values || !returns || !advantages || !stats || T <= 0 || N <= 0) return -1;
+  if ((N + 255) / 256 > DET_MAX_BLOCKS) return -1;                      // one row of det_gae_slab per workgroup
   gae_kernel<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(rewards, dones, values, last_values, T, N, gamma, lam,
                                                                                       returns, advantages, stats);
   return hipGetLastError() == hipSuccess ? 0 : -9;

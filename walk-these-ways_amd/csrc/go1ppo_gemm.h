@@ -299,7 +299,8 @@ extern "C" int go1ppo_gemm_nt(const Go1PpoGemmArgs* a, void* stream) {
 //     (Go1PpoWgradProblem.partials, plain stores; summed in a fixed order by the optimiser's norm pass or go1ppo_grad_reduce) — or, without
 //     slabs, meet in fp32 atomics on the gradient buffer itself (~200 G atomic adds/s chip-wide: 15.6 of the 64.5 us of the PPO pass's
 //     launch, which is why the product path uses slabs); the bias gradient (column sums of dZ) is one more MFMA per fragment against a
-//     fragment of ones, in the workgroups of the first column tile (atomics in both modes: n values per workgroup).
+//     fragment of ones, in the workgroups of the first column tile, stored as the row chunk's row of a bias slab and summed in chunk
+//     order by the last of those workgroups (det_last, go1ppo.hip): the same bias gradient in every run.
 // rows % 64 == 0, n % 8 == 0, k % 8 == 0.
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;
 typedef __attribute__((ext_vector_type(8))) short s16x8_t;
@@ -459,7 +460,7 @@ __device__ __forceinline__ void wgrad_tn_body(const bf16_t* P, int ldp, const bf
           else atomicAdd(C + (int64_t)n * ldc + k, acc[a][b][e]);
         }
       }
-      if (do_bias && i16 == 0) atomicAdd(bias_grad + n, bacc[a][e]);
+      if (do_bias && i16 == 0) bias_grad[n] = bacc[a][e];       // this row chunk's row of the bias slab (wgrad_tn_batched_kernel)
     }
   }
 }
@@ -601,7 +602,7 @@ __device__ __forceinline__ void wgrad_tn_body_wide(const bf16_t* P, int ldp, con
           else atomicAdd(C + (int64_t)n * ldc + k, acc[a][b][e]);
         }
       }
-      if (do_bias && i16 == 0) atomicAdd(bias_grad + n, bacc[a][e]);
+      if (do_bias && i16 == 0) bias_grad[n] = bacc[a][e];       // this row chunk's row of the bias slab (wgrad_tn_batched_kernel)
     }
   }
 }
@@ -633,13 +634,28 @@ __global__ __launch_bounds__(WTN_THREADS, 1) void wgrad_tn_batched_kernel(const 
   const bool slab = P.partials != nullptr;
   float* C = slab ? P.partials + (int64_t)split * P.partial_stride : P.dW;
   const int steps = (int)((m_end - m_begin) / WTN_STEP);
+  // bias: the workgroups of the first column tile store their column sums as row `split` of the (problem, n tile) bias slab, indexed by n
+  const int nt = tile / tiles_k, n0 = nt * (wide ? 2 * WTN_T : WTN_T);
+  const bool bias = P.bias_grad != nullptr && tile % tiles_k == 0;
+  float* bias_slab = det_tn_slab + (int64_t)(p * DET_TN_MAXNT + nt) * DET_TN_MAXS * DET_TN_W;
+  float* bias_row = bias ? bias_slab + (int64_t)split * DET_TN_W - n0 : nullptr;
   if (wide)
-    wgrad_tn_body_wide((const bf16_t*)P.dz, P.ld_dz, (const bf16_t*)P.h, P.ld_h, m_begin, steps, C, P.ldw, P.bias_grad, P.n, P.k,
-                       (tile / tiles_k) * 2 * WTN_T, (tile % tiles_k) * WTN_T, lds_raw, P.zero_n, P.zero_k0, P.zero_k1, slab);
+    wgrad_tn_body_wide((const bf16_t*)P.dz, P.ld_dz, (const bf16_t*)P.h, P.ld_h, m_begin, steps, C, P.ldw, bias_row, P.n, P.k,
+                       n0, (tile % tiles_k) * WTN_T, lds_raw, P.zero_n, P.zero_k0, P.zero_k1, slab);
   else
-    wgrad_tn_body((const bf16_t*)P.dz, P.ld_dz, (const bf16_t*)P.h, P.ld_h, m_begin, steps, C, P.ldw, P.bias_grad, P.n, P.k,
-                  (tile / tiles_k) * WTN_T, (tile % tiles_k) * WTN_T, reinterpret_cast<bf16_t (*)[2][WTN_STEP * WTN_T]>(lds_raw), P.zero_n, P.zero_k0,
+    wgrad_tn_body((const bf16_t*)P.dz, P.ld_dz, (const bf16_t*)P.h, P.ld_h, m_begin, steps, C, P.ldw, bias_row, P.n, P.k,
+                  n0, (tile % tiles_k) * WTN_T, reinterpret_cast<bf16_t (*)[2][WTN_STEP * WTN_T]>(lds_raw), P.zero_n, P.zero_k0,
                   P.zero_k1, slab);
+  if (!bias) return;
+  const int splits = (int)((P.rows + P.chunk_rows - 1) / P.chunk_rows);
+  if (!det_last(&det_count[DET_TN + p * DET_TN_MAXNT + nt], (unsigned)splits)) return;
+  const int width = (wide ? 2 * WTN_T : WTN_T) < P.n - n0 ? (wide ? 2 * WTN_T : WTN_T) : P.n - n0;
+  for (int c = threadIdx.x; c < width; c += blockDim.x) {
+    float t = 0.f;
+#pragma unroll 16
+    for (int sp = 0; sp < splits; sp++) t += bias_slab[(int64_t)sp * DET_TN_W + c];
+    P.bias_grad[n0 + c] += t;
+  }
 }
 
 extern "C" int go1ppo_wgrad_tn_plan(Go1PpoWgradProblem* probs, int count) {
@@ -675,7 +691,14 @@ extern "C" int go1ppo_wgrad_tn_plan(Go1PpoWgradProblem* probs, int count) {
       P.wg_offset = total;
       total += (int)((steps + cs - 1) / cs) * wtn_tiles_n(P) * ((P.k + WTN_T - 1) / WTN_T);
     }
-    if (total <= cus * rounds || chunk_steps >= 4096) return total;
+    if (total <= cus * rounds || chunk_steps >= 4096) {
+      for (int i = 0; i < count; i++) {                           // the bias slabs (go1ppo.hip, fixed-order sums) must hold the plan
+        const Go1PpoWgradProblem& P = probs[i];
+        if (P.bias_grad && (i >= DET_TN_MAXP || wtn_tiles_n(P) > DET_TN_MAXNT || (P.rows + P.chunk_rows - 1) / P.chunk_rows > DET_TN_MAXS))
+          return -2;
+      }
+      return total;
+    }
   }
 }
 
