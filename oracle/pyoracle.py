@@ -11,34 +11,26 @@ import sys
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_PKG = os.path.join(_HERE, "..", "walk-these-ways_amd")
-for p in (_PKG, os.path.join(_PKG, "shims")):
+_REPO = os.path.dirname(_HERE)
+_PKG = os.path.join(_REPO, "walk-these-ways_amd")
+for p in (_REPO, _PKG, os.path.join(_PKG, "shims")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
 import go1sim_abi as abi  # noqa: E402
+from __graft_entry__ import source_hash  # noqa: E402
 
 LIB = os.path.join(_HERE, "_build", "libgo1oracle.so")
 LIB32 = os.path.join(_HERE, "_build", "libgo1oracle32.so")        # the same restatement with real = float (Makefile)
-
-
-def _content_hash():
-    import hashlib
-    h = hashlib.sha256()
-    csrc = os.path.join(_PKG, "csrc")
-    for f in (os.path.join(_HERE, "go1_oracle.c"), os.path.join(_HERE, "Makefile"), os.path.join(_HERE, "..", "include", "go1sim.h"),
-              os.path.join(csrc, "go1_model_data.h"), os.path.join(csrc, "go1_actuator_data.h")):
-        h.update(os.path.basename(f).encode() + b"\0")
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-    return h.hexdigest()[:16]
 
 
 def build(force=False):
     """make both libraries; rebuilt whenever the hash of the sources (content, not mtimes: as __graft_entry__.build_hip) differs from the one
     recorded beside them"""
     stamp = os.path.join(_HERE, "_build", "stamp")
-    want = _content_hash()
+    csrc = os.path.join(_PKG, "csrc")
+    want = source_hash([os.path.join(_HERE, "go1_oracle.c"), os.path.join(_HERE, "Makefile"), os.path.join(_REPO, "include", "go1sim.h"),
+                        os.path.join(csrc, "go1_model_data.h"), os.path.join(csrc, "go1_actuator_data.h")], [])
     fresh = os.path.exists(LIB) and os.path.exists(LIB32) and os.path.exists(stamp) and open(stamp).read().strip() == want
     if force or not fresh:
         subprocess.check_call(["make", "-C", _HERE, "-B", "-s"])

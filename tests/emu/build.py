@@ -3,23 +3,16 @@ unmodified) compiled for the HOST against the SIMT emulator in this directory.  
 exercise the real device code without a GPU; the product never loads this library."""
 import os
 import subprocess
+import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.abspath(os.path.join(HERE, "..", ".."))
+if REPO not in sys.path:
+    sys.path.insert(0, REPO)
+from __graft_entry__ import source_hash  # noqa: E402
 CSRC = os.path.join(REPO, "walk-these-ways_amd", "csrc")
 OUT = os.path.join(HERE, "_build", "libgo1sim_emu.so")
 CLANG = os.environ.get("EMU_CXX", "/opt/rocm/lib/llvm/bin/clang++")
-
-
-def content_hash(files, flags):
-    import hashlib
-    h = hashlib.sha256()
-    for f in files:
-        h.update(os.path.basename(f).encode() + b"\0")
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-    h.update(" ".join(flags).encode())
-    return h.hexdigest()[:16]
 
 
 def build(force=False, defines=(), tag=""):
@@ -28,7 +21,7 @@ def build(force=False, defines=(), tag=""):
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".h", ".hip"))]
     deps += [os.path.join(HERE, "hip", "hip_runtime.h"), os.path.join(HERE, "emu_runtime.cpp"), os.path.join(REPO, "include", "go1sim.h")]
     flags = ["-x", "c++", "-std=c++17", "-O1", "-g", "-fPIC", "-shared", "-fopenmp", "-ffp-contract=off", "-Wno-everything"] + ["-D" + d for d in defines]
-    want = content_hash(sorted(deps), flags)          # content, not mtimes (as __graft_entry__.build_hip): a stale emulator cannot pass for the sources
+    want = source_hash(sorted(deps), flags)          # content, not mtimes (as __graft_entry__.build_hip): a stale emulator cannot pass for the sources
     stamp = out + ".stamp"
     if not force and os.path.exists(out) and os.path.exists(stamp) and open(stamp).read().strip() == want:
         return out

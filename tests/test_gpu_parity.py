@@ -474,18 +474,16 @@ ROW_TOL = (("obs_buf", 3e-3, 1e-3), ("privileged_obs_buf", 1e-5, 0), ("obs_histo
 
 
 # Cross-check of the frozen attribution constants (the review of round 4, item 7): the `-alt` cases of test_product_instances_match_oracle (suite
-# members since round 6; GO1_PARITY_ALT=1 still switches every product run over) re-run the 4096-environment product-instance
-# tests with ANOTHER seed for states / domain randomisation / action stream and ANOTHER relief (rough_field seed) — same constants, same rules.
-# The summaries of both settings are committed side by side (profiles/r05_parity_rates.txt, r05_parity_rates_alt_seed.txt).
-PARITY_ALT = os.environ.get("GO1_PARITY_ALT", "0") == "1"
+# members since round 6) re-run the 4096-environment product-instance tests with ANOTHER seed for states / domain randomisation / action
+# stream and ANOTHER relief (rough_field seed) — same constants, same rules.  The summaries of both settings are committed side by side
+# (profiles/r05_parity_rates.txt, r05_parity_rates_alt_seed.txt).
 
 
-def run_full_step_comparison(variant, N, steps, seed=11, prepare=None, watch=None, what="full step", product=False, alt=None):
+def run_full_step_comparison(variant, N, steps, seed=11, prepare=None, watch=None, what="full step", product=False, alt=False):
     """HIP step vs oracle step on identical state / action / RNG streams, re-synchronised after every step so that each
     step is compared on its own (a free-running pair diverges through contact-mode flips, as two fp32 PhysX runs
     would).  Every environment outside the per-quantity tolerances must be attributed (module docstring); returns the
     Attribution record and event counts."""
-    alt = (PARITY_ALT if alt is None else alt) and product
     if alt:
         seed, what = seed + 1000, what + " (alt seed)"
     cfg, S, meta, Bc, orc = gpu_pair(variant, N, seed=seed)
@@ -747,7 +745,7 @@ def test_physics_substep_on_height_field(scenario, walls):
     assert wall_contacts == 0 if not walls else (wall_contacts > 0 or scenario == "standing"), wall_contacts       # the vertical faces were hit
 
 
-def run_height_field_comparison(walls, N=256, steps=40, product=False, residual=(0, 0.0), alt=None):
+def run_height_field_comparison(walls, N=256, steps=40, product=False, residual=(0, 0.0), alt=False):
     """full steps on the rough int16 height field of rough_field(): 187-point height scan in the observation, resets onto the
     field, the height-relative termination test (legged_robot.py:160-178, 1793-1806); walls: as a `trimesh` terrain (vertical
     risers).  product: the instance the product launches (no signature code) beside its `_sig` twin."""
@@ -757,7 +755,6 @@ def run_height_field_comparison(walls, N=256, steps=40, product=False, residual=
           "env": dict(observe_heights=True, num_observations=70 + 187),
           "domain_rand": dict(randomize_gravity=False)}
     import pyoracle
-    alt = (PARITY_ALT if alt is None else alt) and product
     cfg, S, meta, Bc = make_sim("train_noise", N, seed=1013 if alt else 13, extra=ex)
     hs, hscale, vscale = rough_field(seed=1002 if alt else 2)
     H.bind_height_field(S, Bc, hs, hscale, vscale, 0.0, slope_threshold=0.75 if walls else None)
@@ -826,7 +823,7 @@ def test_full_step_on_height_field(walls):
 
 # (instance, environments, steps, alt): the three instances at configs[1] / [2]'s 4096 environments; round 6 (the review of round 5): plane and walls at
 # configs[4]'s per-GPU size — 8192 environments = 512 workgroups on 256 CUs: the only regime in which a workgroup starts on a CU whose LDS the
-# previous one just left (step_body zero-fills `lds` / `ldsx`) — and the second seed / second relief that used to sit behind GO1_PARITY_ALT=1
+# previous one just left (step_body zero-fills `lds` / `ldsx`) — and the second seed / second relief (the `-alt` cases)
 PRODUCT_CASES = [("plane", 4096, 40, False), ("hf", 4096, 40, False), ("walls", 4096, 40, False),
                  ("plane", 8192, 10, False), ("hf", 8192, 10, False), ("walls", 8192, 10, False),
                  ("plane", 4096, 40, True), ("hf", 4096, 40, True), ("walls", 4096, 40, True)]

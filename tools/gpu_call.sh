@@ -7,13 +7,11 @@ run() { name=$1; shift; echo "=== $name: $*" | tee -a $OUT/index.txt; ( time tim
 for step in "$@"; do
 case $step in
   parity) GO1_PARITY_LOG=$PWD/$OUT/parity_rates.txt run parity python -m pytest tests/test_gpu_parity.py tests/test_gpu_env.py -q -s -k "product_instances or train_eval_split or deferred_torque" ;;
-  altseed) GO1_PARITY_ALT=1 GO1_PARITY_LOG=$PWD/$OUT/parity_rates_alt_seed.txt run altseed python -m pytest tests/test_gpu_parity.py -q -s -k "product_instances" ;;
   pmc) GRAFT_REPO_ROOT=${GRAFT_REPO_ROOT:-$PWD} run pmc bash tools/pmc.sh $TAG ;;
   quick) GO1_PARITY_LOG=$PWD/$OUT/parity_rates.txt run quick python -m pytest tests/test_gpu_parity.py tests/test_gpu_env.py tests/test_gpu_ppo_reference.py -q -k "product_instances or failed or full_step_matches or ragged or deferred_torque or gpu_fp32_update or history" ;;
   fusedtests) run fusedtests python -m pytest tests/test_gpu_ppo_fused.py -q -x ;;
   gemm) run gemm python tools/bench_gemm.py ;;
   bench) run bench python bench.py --steps 20 --warmup 5 --headline-only --no-cpu-baseline --breakdown ;;
-  bench_atomics) GO1_WGRAD_SLABS=0 run bench_atomics python bench.py --steps 20 --warmup 5 --headline-only --no-cpu-baseline --breakdown ;;
   disttests) run disttests python -m pytest tests/test_gpu_distributed.py -q -x ;;
   benchfull) TMO=900 run benchfull python bench.py ;;
   prof) (cd /tmp; rocprofv3 --kernel-trace --stats --output-format csv -d $OLDPWD/$OUT/prof -- python $OLDPWD/bench.py --steps 3 --warmup 2 --headline-only --no-cpu-baseline) > $OUT/prof.log 2>&1; find $OUT/prof -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats.csv \; ; for t in $(find $OUT/prof -name "*kernel_trace.csv"); do python tools/timeline.py $t --which -3 > $OUT/timeline.txt 2>&1; python tools/timeline.py $t --anchor mse_kernel --which -3 >> $OUT/timeline.txt 2>&1; python tools/timeline.py $t --anchor go1_step_kernel --which -5 > $OUT/timeline_rollout.txt 2>&1; done; find $OUT/prof -type f ! -name "*stats*" -delete; echo "=== prof rc=$?" | tee -a $OUT/index.txt ;;

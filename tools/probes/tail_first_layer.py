@@ -1,6 +1,6 @@
 """Probe: how fast is "row tile resident in LDS (ELU applied on the way in), weights streamed from L2 straight into MFMA operands" for
 the actor's and critic's 512 -> 256 layer at 24576 rows?  go1ppo_tail_fwd restricted to ONE layer per net, with and without its
-(2-byte, fragment-shaped) global stores, 32 and 64 rows per workgroup (GO1PPO_TAIL_BM64=1).  Against: go1ppo_elu_fwd + go1ppo_gemm_nt_pair
+(2-byte, fragment-shaped) global stores, 32 rows per workgroup.  Against: go1ppo_elu_fwd + go1ppo_gemm_nt_pair
 (the update's current path).  GPU box only."""
 import ctypes
 import os
@@ -54,7 +54,7 @@ for store in (False, True):
             L.W, L.bias, L.out, L.n_out, L.k_in, L.ld_out, L.elu = W[n].data_ptr(), b[n].data_ptr(), outs[n].data_ptr() if store else None, 256, 512, 256, 0
         sets.append((a, outs))
     t = timeit([lambda q=q: lib.go1ppo_tail_fwd(ctypes.byref(q[0]), s) for q in sets])
-    print(f"tail_fwd, one 512 -> 256 layer x 2 nets, rows/workgroup {'64' if os.environ.get('GO1PPO_TAIL_BM64') else '32'}, global stores {store}: {t:6.1f} us")
+    print(f"tail_fwd, one 512 -> 256 layer x 2 nets, rows/workgroup 32, global stores {store}: {t:6.1f} us")
 Z = [[torch.zeros(M, 256, **bf) for _ in range(2)] for _ in range(R)]
 t_elu = timeit([lambda i=i: lib.go1ppo_elu_fwd(Y1[i][:, 256:].data_ptr(), M, 1024, 1280, lat.data_ptr(), 64, 2, wz.data_ptr(), 64, 512, s) for i in range(R)])
 t_pair = timeit([lambda i=i: fused.gemm_nt_pair(lib, dict(a=Y1[i][:, 256:768], b=W[0], c=Z[i][0], bias=b[0]), dict(a=Y1[i][:, 768:], b=W[1], c=Z[i][1], bias=b[1]))

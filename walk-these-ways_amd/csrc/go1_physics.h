@@ -957,7 +957,6 @@ DEV void physics_substep(CfgRef cfg, BufRef B, const SolverLds& Z, int lane, int
           V3 l = v3(hc.x, hc.y + (m ? 1.f : -1.f) * (float)GO1_HIP_CAPSULE_HALF, hc.z);
           cand_try<WALLS, false, PLANE>(cfg, hs, ch[m], nowall, p[0] + mul(R[0], l), s.pos, (float)GO1_HIP_CAPSULE_RADIUS, v[0], m);      // (same top surface as every other shape)
         }
-#ifndef GO1_ABLATE_CAND
 #pragma unroll
         for (int en = 0; en < 2; en++) {       // thigh / calf boxes: long axis z -> ends by the sign of z (corner bit 2)
           // on the plane the deepest corner of an end minimises z = ... + sx hx R.c0.z + sy hy R.c1.z: sx = -sign(R.c0.z), sy likewise
@@ -973,7 +972,6 @@ DEV void physics_substep(CfgRef cfg, BufRef B, const SolverLds& Z, int lane, int
           cand_try<false, false, true>(cfg, hs, ct[en], cwt, p[1] + mul(R[1], lt), s.pos, 0.f, v[1], mt);
           cand_try<false, false, true>(cfg, hs, ck[en], cwk, p[2] + mul(R[2], lk), s.pos, 0.f, v[2], mk);
         }
-#endif
         cand_try<WALLS, WALLS, PLANE>(cfg, hs, cf, cwf, p[2] + mul(R[2], model_v3(GO1_FOOT_OFFSET, leg)), s.pos, (float)GO1_FOOT_RADIUS, v[2], 0);
       } else {
         // Height field: 19 points per lane (2 hip capsule ends, 8 + 8 box corners, the foot), each a cell look-up.  The look-ups run one
@@ -999,14 +997,11 @@ DEV void physics_substep(CfgRef cfg, BufRef B, const SolverLds& Z, int lane, int
         }
         const V3 xf = p[2] + mul(R[2], model_v3(GO1_FOOT_OFFSET, leg));
         terrain_fetch(cfg, hs, s.pos.x + xf.x, s.pos.y + xf.y, ff);
-#ifndef GO1_ABLATE_CAND
         xc = thigh_corner(0);
         terrain_fetch(cfg, hs, s.pos.x + xc.x, s.pos.y + xc.y, cur);
-#endif
 #pragma unroll
         for (int m = 0; m < 2; m++) cand_eval<WALLS, false>(cfg, fh[m], ch[m], nowall, xh[m], s.pos, (float)GO1_HIP_CAPSULE_RADIUS, v[0], m, cd);
         cand_eval<WALLS, WALLS>(cfg, ff, cf, cwf, xf, s.pos, (float)GO1_FOOT_RADIUS, v[2], 0, cd);
-#ifndef GO1_ABLATE_CAND
 #pragma unroll
         for (int en = 0; en < 2; en++) {       // thigh / calf boxes: long axis z -> ends by the sign of z (corner bit 2)
 #pragma unroll 1
@@ -1024,7 +1019,6 @@ DEV void physics_substep(CfgRef cfg, BufRef B, const SolverLds& Z, int lane, int
             cur = nxt; xc = xn;
           }
         }
-#endif
       }
       pthigh = p[1]; pknee = p[2]; pfoot = p[2] + mul(R[2], model_v3(GO1_FOOT_OFFSET, leg));
       vthigh = v[1]; vlow = v[2]; vhip = v[0];
@@ -1516,7 +1510,6 @@ DEV void physics_substep(CfgRef cfg, BufRef B, const SolverLds& Z, int lane, int
   const float mu_s = 0.5f * (s.mu + cfg.terrain_friction);       // PhysX default combine mode: average
   const float mu_d = fminf(0.5f * (s.mu + cfg.terrain_dynamic_friction), mu_s);
   float lamj[3] = {0.f, 0.f, 0.f};                                 // limit impulses of the own joints
-#ifndef GO1_ABLATE_PGS
   {
     SweepState st;
     st.z01 = st.z23 = st.z45 = st.y01 = splat2(0.f);
@@ -1775,7 +1768,6 @@ DEV void physics_substep(CfgRef cfg, BufRef B, const SolverLds& Z, int lane, int
     }
     if (SIG && B.contact_signature != nullptr && sub < GO1_SIG_MAX_SUBSTEPS && leg == 0) AT(B.contact_signature, sub * GO1_SIG_WORDS + 3, e) += sig_active;
   }
-#endif
 
   LDS_PHASE();
   PROF(5);

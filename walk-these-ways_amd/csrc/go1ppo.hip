@@ -238,11 +238,7 @@ __device__ __forceinline__ void block_reduce_store(float (&v)[NV], float* const 
   if (threadIdx.x < NV) {
     float t = 0.f;
     for (int w = 0; w < (int)(blockDim.x >> 6); w++) t += lds[w * NV + threadIdx.x];
-#if defined(LOSS_ABLATE) && (LOSS_ABLATE & 8)
-    if (dst[threadIdx.x] && t == 12345.678f) *dst[threadIdx.x] = t;      // probe build: the reduction without its cross-workgroup sums
-#else
     if (dst[threadIdx.x]) *dst[threadIdx.x] = t;
-#endif
   }
 }
 
@@ -254,18 +250,6 @@ __device__ __forceinline__ void block_reduce_store(float (&v)[NV], float* const 
 //   branches coincide and torch.max splits the gradient half/half onto two identical paths), else 0
 //   value loss: max((v-R)^2, (v_old + clamp(v - v_old, -eps, eps) - R)^2), same tie rule
 //   entropy = sum log sigma + const (independent of the sample)
-#if defined(LOSS_ABLATE) && (LOSS_ABLATE & 2)
-#define LOSS_LOG(x) __logf(x)
-#define LOSS_EXP(x) __expf(x)
-#else
-#define LOSS_LOG(x) logf(x)
-#define LOSS_EXP(x) expf(x)
-#endif
-#if defined(LOSS_ABLATE) && (LOSS_ABLATE & 4)
-#define LOSS_NO_STORES 1
-#else
-#define LOSS_NO_STORES 0
-#endif
 // one sample: losses and the analytic gradient w.r.t. its head outputs (written to d_mean / d_value); the sample's shares of the sums
 // come back in sur / vl / kl / dvb / dstd[] / dmb[] (zero for a thread past the last row)
 __device__ __forceinline__ void loss_sample(const Go1PpoLossArgs& a, int64_t r, float& sur, float& vl, float& kl, float& dvb,
@@ -281,9 +265,6 @@ __device__ __forceinline__ void loss_sample(const Go1PpoLossArgs& a, int64_t r, 
   for (int j = 0; j < GO1PPO_MAX_ACTIONS; j++) dstd[j] = dmb[j] = 0.f;
   if (on) {
     int64_t s = a.idx[r];
-#if defined(LOSS_ABLATE) && (LOSS_ABLATE & 1)
-    s = r;                       // probe build (tools/probes/loss_ablate.py): storage rows in order instead of through the permutation
-#endif
     const bf16_t* mrow = reinterpret_cast<const bf16_t*>(a.mean) + r * a.head_ld;
     float mu[GO1PPO_MAX_ACTIONS], z[GO1PPO_MAX_ACTIONS], isg[GO1PPO_MAX_ACTIONS];
     float act[GO1PPO_MAX_ACTIONS], omu[GO1PPO_MAX_ACTIONS], osg[GO1PPO_MAX_ACTIONS];
@@ -317,13 +298,13 @@ __device__ __forceinline__ void loss_sample(const Go1PpoLossArgs& a, int64_t r, 
         float sg = a.std[j];
         isg[j] = 1.f / sg;
         z[j] = (act[j] - mu[j]) * isg[j];
-        logp += -0.5f * z[j] * z[j] - LOSS_LOG(sg) - HALF_LOG_2PI;
+        logp += -0.5f * z[j] * z[j] - logf(sg) - HALF_LOG_2PI;
         float so = osg[j], dm = omu[j] - mu[j];
-        kl += LOSS_LOG(sg / so + 1.e-5f) + (so * so + dm * dm) / (2.f * sg * sg) - 0.5f;
+        kl += logf(sg / so + 1.e-5f) + (so * so + dm * dm) / (2.f * sg * sg) - 0.5f;
       }
     }
     float adv = a.advantages[s];
-    float ratio = LOSS_EXP(logp - a.old_logp[s]);
+    float ratio = expf(logp - a.old_logp[s]);
     float lo = 1.f - a.clip_param, hi = 1.f + a.clip_param;
     float rc = fminf(fmaxf(ratio, lo), hi);
     float s1 = -adv * ratio, s2 = -adv * rc;
@@ -342,12 +323,12 @@ __device__ __forceinline__ void loss_sample(const Go1PpoLossArgs& a, int64_t r, 
           const int j = j0 + q;
           if (j < A) {
             gq[q] = f2bf(dlogp * z[j] * isg[j]);
-            if (!LOSS_NO_STORES && !st4) drow[j] = gq[q];
+            if (!st4) drow[j] = gq[q];
             dmb[j] = bf2f(gq[q]);
             dstd[j] = dlogp * (z[j] * z[j] - 1.f) * isg[j];
           }
         }
-        if (!LOSS_NO_STORES && st4) {
+        if (st4) {
           uint2 o;
           o.x = (uint32_t)gq[0] | ((uint32_t)gq[1] << 16);
           o.y = (uint32_t)gq[2] | ((uint32_t)gq[3] << 16);
@@ -370,7 +351,7 @@ __device__ __forceinline__ void loss_sample(const Go1PpoLossArgs& a, int64_t r, 
       dv = 2.f * (v - R);
     }
     bf16_t g = f2bf(a.value_loss_coef * dv * invM);
-    if (!LOSS_NO_STORES) reinterpret_cast<bf16_t*>(a.d_value)[r * a.head_ld] = g;
+    reinterpret_cast<bf16_t*>(a.d_value)[r * a.head_ld] = g;
     dvb = bf2f(g);
     kl *= invM;
   }
@@ -408,9 +389,6 @@ __global__ __launch_bounds__(256) void loss_kernel(Go1PpoLossArgs a) {
       __syncthreads();
     }
   }
-#if defined(LOSS_ABLATE) && (LOSS_ABLATE & 8)
-  return;                                                                 // probe build: no cross-workgroup sums
-#endif
   if (!det_last(&det_count[DET_LOSS], gridDim.x)) return;
   for (int c = threadIdx.x; c < 4 + 2 * A; c += blockDim.x) {
     float t = 0.f;
@@ -937,7 +915,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* p, float* g, float* m,
 // (M = 24576 or 4096 rows, N <= 256).  out = elu(in W^T + b) per layer (no ELU on the head); intermediate
 // activations are also written to global memory when the backward pass needs them.
 #define TF_MAXK 512
-template <int BM>          // rows per workgroup: 32 (small batches: more workgroups) or 64 (large: half the weight traffic)
+template <int BM>          // rows per workgroup (go1ppo_tail_fwd launches 32)
 __global__ __launch_bounds__(256) void tail_fwd_kernel(Go1PpoTailArgs A) {
   constexpr int RT = BM / 16;                                            // 16-row MFMA tiles per workgroup
   __shared__ __attribute__((aligned(16))) bf16_t act[2][BM][TF_MAXK + 8];
@@ -1424,11 +1402,7 @@ extern "C" int go1ppo_tail_fwd(const Go1PpoTailArgs* args, void* stream) {
     }
     if (N.rows > max_rows) max_rows = N.rows;
   }
-  static const bool bm64 = getenv("GO1PPO_TAIL_BM64") != nullptr;      // probe switch (tools/probes/tail_first_layer.py)
-  if (bm64)
-    tail_fwd_kernel<64><<<dim3((unsigned)((max_rows + 63) / 64), args->num_nets), dim3(256), 0, (hipStream_t)stream>>>(*args);
-  else
-    tail_fwd_kernel<32><<<dim3((unsigned)((max_rows + 31) / 32), args->num_nets), dim3(256), 0, (hipStream_t)stream>>>(*args);
+  tail_fwd_kernel<32><<<dim3((unsigned)((max_rows + 31) / 32), args->num_nets), dim3(256), 0, (hipStream_t)stream>>>(*args);
   return hipGetLastError() == hipSuccess ? 0 : -9;
 }
 

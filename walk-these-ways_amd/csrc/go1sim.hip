@@ -118,11 +118,7 @@ DEV void step_body(const StepArgs& A, float* lds, lf4* ldsx, float* act_lds, flo
   const bool full_wave = (int)(blockIdx.x + 1) * EPW <= N;      // the MFMA torque model needs all 64 lanes
   const bool substep_only = A.mode == 2;                         // piecewise entry point: ONE physics substep with the torques in the buffer
   const bool mfma_torque = full_wave && cfg.control_type == 1 && !substep_only;
-#if defined(GO1_ABLATE_TORQUE) || defined(GO1_ABLATE_PHYSICS) || defined(GO1_NO_DEFERRED_TORQUE)
-  const bool deferred = false;
-#else
   const bool deferred = mfma_torque && nw == 4 && cfg.decimation <= ACT_MAX_DEC;     // torque model entirely on the helper wavefronts (3 x 64 lanes = the 192 rows)
-#endif
   if (mfma_torque && wv == 0) actuator_lds_init(act_lds, lane);
   reward_plan_to_lds(csc->rew, plan_lds, (int)threadIdx.x);
   PROF_INIT
@@ -132,7 +128,6 @@ DEV void step_body(const StepArgs& A, float* lds, lf4* ldsx, float* act_lds, flo
   if (wv != 0) {           // helper wavefront: the same sequence of workgroup barriers as the master's substep loop
 #pragma unroll 1
     for (int sub = 0; sub < nsub; sub++) {
-#ifndef GO1_ABLATE_TORQUE
       if (substep_only) {
       } else if (deferred) {
         BLOCK_SYNC(nw);                                   // the master's q, qd are in the row slots
@@ -141,14 +136,10 @@ DEV void step_body(const StepArgs& A, float* lds, lf4* ldsx, float* act_lds, flo
         actuator_tiles(act_lds, Z.act_io(), lane, 4 * (wv - 1), 1, 4 * wv);
         BLOCK_SYNC(nw);                                   // (the master arrives here when it needs the torques)
       } else if (mfma_torque) actuator_net_mfma(act_lds, Z.act_io(), lane, wv, nw, false, nullptr, nullptr);
-#endif
-#ifndef GO1_ABLATE_PHYSICS
       BLOCK_SYNC(nw);                                     // the master's items and hand-over packets are in LDS
       emit_terrain_contacts(cfg, Z, lane >> 2, 4 * (wv - 1) + (lane & 3), 4 * (nw - 1), cfg.sim_dt);
       BLOCK_SYNC(nw);
-#endif
     }
-#ifndef GO1_ABLATE_POST
     if (!substep_only) {       // post_physics(): the observations on helper 1 while the master evaluates the rewards (go1_maps.h)
       BLOCK_SYNC(nw);          // S1
       // round 0: the usual step (acth[0], written before S1).  round 1: the late hand-over — a reset kept the observations back until the
@@ -172,7 +163,6 @@ DEV void step_body(const StepArgs& A, float* lds, lf4* ldsx, float* act_lds, flo
         if (acth[1] == 0.f) break;
       }
     }
-#endif
     return;
   }
   const float h = cfg.sim_dt;
@@ -235,22 +225,18 @@ DEV void step_body(const StepArgs& A, float* lds, lf4* ldsx, float* act_lds, flo
   PROF(0);
   auto substep = [&](int sub) __attribute__((always_inline)) {
     PROF(24);
-#ifndef GO1_ABLATE_TORQUE
     if (substep_only) {
     } else if (deferred) {
       torque_post_state(L, Z.act_io(), lane);
       PROF(22);
       BLOCK_SYNC(nw);
     } else compute_torques(cfg, B, L, leg, e, N, head, act_lds, Z.act_io(), mfma_torque, nw, fault);
-#endif
     PROF(1);
     head = (head + 1) % nl;
-#ifndef GO1_ABLATE_PHYSICS
     physics_substep<WALLS, SIG, PLANE>(cfg, B, Z, lane, nw, s, L, grav, warm || (cfg.warm_start && sub > 0), h, fault, drops, deferred ? acth : nullptr, e, N, sub PROF_PASS);
-#endif
     PROF(30);
   };
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(GO1_SUBSTEP_LOOP)
+#if defined(__HIP_DEVICE_COMPILE__)
   // The reference's decimation of 4 with the body written out four times (`#pragma unroll` is refused by the optimizer for this loop): no
   // far backward branch at the end of a substep, and `sub` folds into each copy.  Same-box A/B against the loop (gpurun call r5o): 0.1583 /
   // 0.1231 against 0.1626 / 0.1292 ms per env.step (-2.6 % / -4.7 %); code size x 4 (the 16-384 KB probe shows no instruction-cache cliff,
@@ -268,11 +254,9 @@ DEV void step_body(const StepArgs& A, float* lds, lf4* ldsx, float* act_lds, flo
   __threadfence_block();
   LDS_PHASE();
   PROF(7);
-#ifndef GO1_ABLATE_POST
   if (!substep_only)
     post_physics<PLANE>(cfg, B, plan_lds, lds, lane, e, N, A.counter + 1, grav, A.history_slot, fault, (int)blockIdx.x * EPW >= csc->num_train_envs,
                         nw > 1 ? acth : nullptr, nw PROF_PASS);
-#endif
   report_fault(B, e, fault);
   report_drops(B, drops);
 #define PROF_LAUNCH ((unsigned)A.counter)
@@ -527,8 +511,7 @@ static int launch(Go1Sim* s, int mode, const float* actions, const int32_t* ids,
   const int slot = timed ? (int)(s->timing_n % s->timing_cap) : 0;
   if (timed) (void)hipEventRecord(s->ev[2 * slot], st);
   if (mode == 0 || mode == 2) {
-    static const bool force_hf = getenv("GO1_FORCE_HF_INSTANCE") != nullptr;        // A/B of the plane instance (tools/variant_bench.sh)
-    const bool hf = force_hf || (s->cfg.terrain_type != 0 && s->buf.height_samples != nullptr), walls = hf && s->cfg.terrain_type != 0 && s->cfg.hf_wall_units > 0;
+    const bool hf = s->cfg.terrain_type != 0 && s->buf.height_samples != nullptr, walls = hf && s->cfg.terrain_type != 0 && s->cfg.hf_wall_units > 0;
     const bool sig = s->buf.contact_signature != nullptr;
     if (walls) { if (sig) hipLaunchKernelGGL(go1_step_kernel_walls_sig, grid, block, 0, st, A); else hipLaunchKernelGGL(go1_step_kernel_walls, grid, block, 0, st, A); }
     else if (hf) { if (sig) hipLaunchKernelGGL(go1_step_kernel_hf_sig, grid, block, 0, st, A); else hipLaunchKernelGGL(go1_step_kernel_hf, grid, block, 0, st, A); }

@@ -224,16 +224,13 @@ class FusedNet:
         # weight gradients as per-row-chunk SLABS (plain stores) summed in a fixed order by one pass — the optimiser's norm pass when
         # `defer_grad_sum` is set by the owner (FusedAdam.step_(pieces=...)), go1ppo_grad_reduce at the end of the backward pass
         # otherwise — instead of fp32 atomics into the flat gradient (15.6 of the 64.5 us of the PPO pass's batched launch on MI355X,
-        # profiles/r04_wgrad_atomics_probe.txt; and run-to-run reproducible).  GO1_WGRAD_SLABS=0: the atomics.
+        # profiles/r04_wgrad_atomics_probe.txt; and run-to-run reproducible)
         self._grad = grad
-        self._slabs = grad is not None and os.environ.get("GO1_WGRAD_SLABS", "1") == "1"
         self.defer_grad_sum = False
         self._rec_pieces, self._slab_ws, self._last_pieces = None, {}, {}
-        # weight gradients: 128-tile kernel for the batched tails; first layer (PPO pass, adaptation pass) on it or on
-        # hipBLASLt.  GO1_WGRAD = "<tails><ppo W1><adaptation W1>" digits for A/B runs (tools/), default below.
-        knob = os.environ.get("GO1_WGRAD", "101")
-        self._wgrad_tn = knob[0] == "1" and M % 64 == 0
-        self._w1_tn = (self._wgrad_tn and knob[1] == "1", self._wgrad_tn and knob[2] == "1")
+        # weight gradients: 128-tile kernel for the batched tails and the adaptation pass's first layer; the PPO pass's first
+        # layer on hipBLASLt (`_big_wgrad`)
+        self._wgrad_tn = M % 64 == 0
         self._tails = self._tails_ad = None
         # measured on MI355X: one fused launch per dependency level beats 8 GEMMs + 5 ELU kernels 3.5x at M = 4096 (32 vs 110 us) — but the
         # engine below (ELU pass, paired 512 -> 256 GEMM, LDS-resident MLP ends) beats it at the rollout's 4096 rows since round 4
@@ -243,7 +240,7 @@ class FusedNet:
         # inference-only engines: the first layer's ELU (+ the actor's latent columns) is applied by the tail kernel while it
         # stages its input rows — two element-wise launches per rollout step less; an engine with a backward pass keeps the
         # separate pass, which leaves the activated first layer in memory for the weight gradients
-        self._elu_on_load = not with_grad and os.environ.get("GO1_ELU_ON_LOAD", "1") == "1"
+        self._elu_on_load = not with_grad
         if fused_tails and self._fused_tails_ok():
             nd, na = self.nd, self.na
             eol = self._elu_on_load
@@ -267,10 +264,10 @@ class FusedNet:
         nt_ok = all(v % 64 == 0 for v in (na1, nc1, self.na, self.n1 - self.nd - self.na)) and \
             all(self.P[k].data_ptr() % 16 == 0 for k in ("actor.1.b", "critic.1.b", "actor.1.W", "critic.1.W"))
         pair_ok = nt_ok and na1 == nc1 and self.na == self.n1 - self.nd - self.na
-        self._l1_nt = os.environ.get("GO1_L1_NT", "1") == "1" and nt_ok
+        self._l1_nt = nt_ok
         # the actor's and the critic's 512 -> 256 GEMMs (forward, input gradient) as one launch each instead of two launches on two
-        # streams: tools/timeline.py showed 5-10 us of idle device at every graph fork and join (GO1_GEMM_PAIR=0: the two streams)
-        self._pair = os.environ.get("GO1_GEMM_PAIR", "1") == "1" and pair_ok
+        # streams: tools/timeline.py showed 5-10 us of idle device at every graph fork and join
+        self._pair = pair_ok
         # the critic's tail is independent of the actor / adaptation chain: it runs on a side stream (forked from and
         # joined back into the caller's stream, so HIP-graph capture records it as a parallel branch)
         self._side = torch.cuda.Stream(device=dev) if two_streams else None
@@ -286,14 +283,12 @@ class FusedNet:
             # the library's single-GEMM kernels split badly (0.74 PFLOP/s); as a BATCHED GEMM over row chunks — a manual
             # split-K, partial products in bf16, summed into the fp32 gradient by the pass that used to be the cast — it
             # runs 25 % faster (tools/probes/wgrad_splitk.py: 4 chunks of 6144 rows at M = 24576)
-            self._w1_split = next((b for b in (M // 6144, 4, 2) if b >= 2 and M % b == 0 and (M // b) % 64 == 0), 1)
-            if os.environ.get("GO1_W1_SPLIT"):
-                self._w1_split = int(os.environ["GO1_W1_SPLIT"])
-            self._w1_tmp = torch.zeros(self._w1_split, self.n1, policy.Kp, **bf)
-            # GO1_DGRAD_NT: the 512 -> 256 input gradients on go1ppo_gemm_nt with the ELU' epilogue instead of hipBLASLt + the
+            w1_split = next((b for b in (M // 6144, 4, 2) if b >= 2 and M % b == 0 and (M // b) % 64 == 0), 1)
+            self._w1_tmp = torch.zeros(w1_split, self.n1, policy.Kp, **bf)
+            # the 512 -> 256 input gradients on go1ppo_gemm_nt with the ELU' epilogue instead of hipBLASLt + the
             # element-wise pass.  In situ A/B on one box: 23.30 vs 23.43 ms per iteration (it was 0.6 ms SLOWER while the
             # epilogue still loaded its ELU' operand where it used it: 19 exposed HBM round trips per workgroup)
-            self._dgrad_nt = os.environ.get("GO1_DGRAD_NT", "1") == "1" and self._mlp2 and nt_ok
+            self._dgrad_nt = self._mlp2 and nt_ok
             self._WT = {n: torch.zeros(self.P[f"{n}.1.W"].shape[1], self.P[f"{n}.1.W"].shape[0], **bf) for n in ("actor", "critic")} \
                 if self._dgrad_nt else None
             # the K-contiguous copies are refreshed per backward pass (two transpose-copy launches) until an optimiser takes them
@@ -487,7 +482,7 @@ class FusedNet:
         self._wgrad(dlat, Z["adaptation"][1], G["adaptation.2.W"], G["adaptation.2.b"])
         self._wgrad(dZ["adaptation"][1], Y1[:, :nd], G["adaptation.1.W"], G["adaptation.1.b"])
         self._join()
-        self._planned_wgrads_beside(lambda: self._big_wgrad(dY1, x, G["W1"], self._w1_tmp, self._w1_tn[0]))
+        self._big_wgrad(dY1, x, G["W1"], self._w1_tmp)
 
     def _forward_adaptation_mlp2(self, x):
         torch.mm(x, self.P["W1"][:self.nd].t(), out=self.Y1d)
@@ -499,7 +494,7 @@ class FusedNet:
         self._mlp2_bwd("adaptation_only", [("adaptation", self.Y1d, d)])
         self._wgrad(dZ["adaptation"][2], Z["adaptation"][1], G["adaptation.2.W"], None)     # head bias: the MSE kernel's
         self._wgrad(dZ["adaptation"][1], self.Y1d, G["adaptation.1.W"], G["adaptation.1.b"])
-        self._big_wgrad(d, x, G["W1"][:nd], self._w1_tmp[:, :nd], self._w1_tn[1])
+        self._big_wgrad(d, x, G["W1"][:nd], self._w1_tmp[:, :nd], own_kernel=self._wgrad_tn)
 
     # ---- K-contiguous weight copies kept by the optimiser ------------------------------------------------------------
     def adam_transposes(self):
@@ -561,18 +556,17 @@ class FusedNet:
             if li > 1:
                 self._elu_bwd(out, h_in, None)
 
-    def _big_wgrad(self, dY, x, gW, tmp, own_kernel):
-        """first-layer weight gradient.  own_kernel: one more problem of the batched 128-tile launch (slabs, or atomics straight
-        into the fp32 gradient); otherwise one (rows x M) @ (M x Kp) bf16 hipBLASLt GEMM (the fp32-output variants it
-        offers for this shape are 3x slower) and one cast into the fp32 gradient."""
+    def _big_wgrad(self, dY, x, gW, tmp, own_kernel=False):
+        """first-layer weight gradient (inside `_run_planned` only).  own_kernel: one more problem of the pass's batched weight-gradient
+        launch; otherwise one (rows x M) @ (M x Kp) bf16 hipBLASLt GEMM (the fp32-output variants it offers for this shape are 3x
+        slower), its partial products summed into the fp32 gradient with the pass's other slab pieces."""
         zr, zc0, zc1 = self.priv_mask           # (gW starts at row 0 of W1: rows of the adaptation module, then the actor's)
         zr = min(zr, gW.shape[0])
         if own_kernel:
             self._wgrad(dY, x, gW, zero=(zr, zc0, zc1))
             return
         b = tmp.shape[0]
-        # the partial products are summed into the fp32 gradient by go1ppo_sum_partials, which also writes the structural zeros
-        # of the privileged-observation columns
+        # (the summing pass also writes the structural zeros of the privileged-observation columns: the piece's `zero`)
         if b == 1 or not tmp.is_contiguous():
             torch.mm(dY.t(), x, out=tmp[0])
             part, count, stride = tmp[0], 1, gW.numel()
@@ -580,13 +574,9 @@ class FusedNet:
             torch.bmm(dY.view(b, dY.shape[0] // b, dY.shape[1]).transpose(1, 2), x.view(b, x.shape[0] // b, x.shape[1]), out=tmp)
             part, count, stride = tmp, b, tmp.stride(0)
         assert gW.is_contiguous() and part.stride(-1) == 1 and part.stride(-2) == gW.shape[1]
-        if self._slabs and (self._recording is not None or self._batched):      # summed with the other slab pieces of the pass
-            if self._rec_pieces is not None:
-                self._rec_pieces.append(dict(begin=self._grad_offset(gW), count=gW.numel(), src=part, stride=stride, kind=2, slabs=count,
-                                             cols=gW.shape[1], zero=(zr, zc0, zc1)))
-            return
-        _chk(self.lib.go1ppo_sum_partials(part.data_ptr(), count, stride, gW.shape[0], gW.shape[1], gW.data_ptr(), zr, zc0, zc1, _stream()),
-             "go1ppo_sum_partials")
+        if self._rec_pieces is not None:       # the recording pass; later passes reuse the table
+            self._rec_pieces.append(dict(begin=self._grad_offset(gW), count=gW.numel(), src=part, stride=stride, kind=2, slabs=count,
+                                         cols=gW.shape[1], zero=(zr, zc0, zc1)))
 
     def _grad_offset(self, view):
         off = (view.data_ptr() - self._grad.data_ptr()) // 4
@@ -614,13 +604,13 @@ class FusedNet:
                 P.rows, P.ld_dz, P.ld_h, P.n, P.k, P.ldw = dz.shape[0], _ld(dz), _ld(h), dz.shape[1], h.shape[1], gW.shape[1]
             tn = self._wgrad_tn and all(P.rows % 64 == 0 and P.n % 8 == 0 and P.k % 8 == 0 for P in tab)
             plan = self.lib.go1ppo_wgrad_tn_plan if tn else self.lib.go1ppo_wgrad_plan
-            if tn and self._slabs:       # the plan depends on WHETHER a problem has slabs (tile shape), not on where they are: a placeholder until they are allocated
+            if tn:       # the plan depends on WHETHER a problem has slabs (tile shape), not on where they are: a placeholder until they are allocated
                 for P, (dz, h, gW, gb, zero) in zip(tab, rec):
                     P.partials, P.partial_stride = 16, gW.numel()
             total = plan(tab, len(rec))
             if total <= 0:
                 raise RuntimeError(f"go1ppo_wgrad_plan failed with code {total}")
-            if tn and self._slabs:
+            if tn:
                 # one fp32 slab per row chunk and problem (shared by the plans of the same pass: graph mode keeps one plan per
                 # pre-gathered input block); zero-initialised and never written on the structural zeros
                 for j, (P, (dz, h, gW, gb, zero)) in enumerate(zip(tab, rec)):
@@ -649,19 +639,14 @@ class FusedNet:
             # the recording pass skipped the launches AND ran the rest of fn: its dgrad results are valid, only the
             # weight gradients are missing -> fall through to the batched launch
         else:
-            self._batched, self._plan_key, self._plan_launched = True, key, False
+            self._batched = True
             try:
                 fn()
             finally:
-                self._batched, self._plan_key = False, None
-            if self._plan_launched:          # fn() put the batched launch on the side stream next to the first-layer GEMM
-                self._finish_pieces(key)
-                return
-        self._launch_plan(key)
-        self._finish_pieces(key)
-
-    def _finish_pieces(self, key):
-        ptab = self._plans[key][5]
+                self._batched = False
+        dev, count, total, _, tn, ptab = self._plans[key]
+        launch = self.lib.go1ppo_wgrad_tn_batched if tn else self.lib.go1ppo_wgrad_batched
+        _chk(launch(dev.data_ptr(), count, total, _stream()), "go1ppo_wgrad_batched")
         self._last_pieces[key[0]] = None
         if ptab is None:
             return
@@ -669,24 +654,6 @@ class FusedNet:
             self._last_pieces[key[0]] = ptab[:2]
         else:
             _chk(self.lib.go1ppo_grad_reduce(self._grad.data_ptr(), ptab[0].data_ptr(), ptab[1], _stream()), "go1ppo_grad_reduce")
-
-    def _launch_plan(self, key):
-        dev, count, total, _, tn, _ = self._plans[key]
-        launch = self.lib.go1ppo_wgrad_tn_batched if tn else self.lib.go1ppo_wgrad_batched
-        _chk(launch(dev.data_ptr(), count, total, _stream()), "go1ppo_wgrad_batched")
-
-    def _planned_wgrads_beside(self, big):
-        """GO1_WGRAD_OVERLAP=1: run `big` (the first-layer weight gradient on hipBLASLt) with the pass's batched small weight
-        gradients on the side stream.  Measured (same box, alternating): 1.5 % SLOWER end to end — both fight for the L2 -> LDS
-        path — so it is off; the sequential order stays the default."""
-        key = getattr(self, "_plan_key", None)
-        if key is None or self._side is None or os.environ.get("GO1_WGRAD_OVERLAP", "0") != "1":
-            return big()
-        with self._branch():
-            self._launch_plan(key)
-        self._plan_launched = True
-        big()
-        self._join()
 
     def backward(self, x):
         # the plan holds device pointers: one per input block (graph mode feeds a different pre-gathered block per mini-batch)
@@ -697,9 +664,9 @@ class FusedNet:
 
     def _backward(self, x):
         """After forward(x) and a loss kernel that filled dZ[actor][last], dZ[critic][last] (+ their bias / std
-        gradients): everything else.  Bias gradients are ACCUMULATED into the (pre-zeroed) flat gradient; weight gradients too without
-        slabs (`_slabs` off) — with slabs they are WRITTEN: by go1ppo_grad_reduce at the end of the pass, or by the optimiser's norm pass
-        (`defer_grad_sum`), see `_run_planned`."""
+        gradients): everything else.  Bias gradients are ACCUMULATED into the (pre-zeroed) flat gradient; weight gradients too when the
+        batched launch has no slabs for them (row counts that are not a multiple of 64) — with slabs they are WRITTEN: by
+        go1ppo_grad_reduce at the end of the pass, or by the optimiser's norm pass (`defer_grad_sum`), see `_run_planned`."""
         nd, na = self.nd, self.na
         G, Y1, dY1, dH1 = self.G, self.Y1, self.dY1, self.dH1
         cols = {"adaptation": slice(0, nd), "actor": slice(nd, nd + na), "critic": slice(nd + na, self.n1)}
@@ -717,13 +684,13 @@ class FusedNet:
         self._tail_bwd("adaptation", Y1[:, :nd], dH1["adaptation"], head_bias_done=False)
         self._elu_bwd(dH1["adaptation"], Y1[:, :nd], None, out=dY1[:, :nd])
         self._join()
-        self._big_wgrad(dY1, x, G["W1"], self._w1_tmp, self._w1_tn[0])
+        self._big_wgrad(dY1, x, G["W1"], self._w1_tmp)
 
     def _backward_adaptation(self, x):
         nd, d = self.nd, self.dH1["adaptation"]
         self._tail_bwd("adaptation", self.Y1d, d)
         self._elu_bwd(d, self.Y1d, None)
-        self._big_wgrad(d, x, self.G["W1"][:nd], self._w1_tmp[:, :nd], self._w1_tn[1])
+        self._big_wgrad(d, x, self.G["W1"][:nd], self._w1_tmp[:, :nd], own_kernel=self._wgrad_tn)
 
     # ---- losses ----------------------------------------------------------------------------------------------
     def ppo_loss(self, st, idx, std, g_std, A, kl, acc):
