@@ -189,6 +189,16 @@ __global__ __launch_bounds__(256) void elu_bwd_tile_kernel(const bf16_t* d, int 
 // Every contributing workgroup STORES its partial values as its own row of a slab (static device buffers below, one per call site);
 // the last contributor to arrive (counted on an integer counter) adds the column sums, taken in row order, to the destinations and
 // resets the counter for the next launch.  Launches of one site follow each other on a stream, so a site's slab is never shared.
+// Publication without a release fence: the L2 is private to each XCD, and an agent-scope release (__threadfence(): buffer_wbl2 sc1)
+// writes back EVERY dirty line of the XCD's L2 — in the weight-gradient kernel the 64-128 KB weight-slab tiles just stored beside the
+// bias row, which nothing in the launch reads (78.6 us per launch with it: profiles/det_sums_kernel_stats.txt; without it:
+// profiles/det_publish_kernel_stats.txt).  Instead
+//   * the slab values are stored WRITE-THROUGH (sc1: det_put, det_put4) and only by the lanes that own them;
+//   * every wave drains its stores (s_waitcnt vmcnt(0), as inline asm: the compiler cannot drop it), the workgroup meets at a barrier,
+//     and one lane takes a ticket with a relaxed agent-scope fetch_add on the site's counter;
+//   * the last arriver alone runs one agent-scope acquire (buffer_inv sc1: this CU's L1 forgets stale copies of the slab) in one lane,
+//     drains it and joins a barrier before its plain loads of the slab; it resets the counter with a relaxed atomic store.
+// The slabs, their row order and the destinations are unchanged, so the sums are bit for bit what the fenced form computed.
 #define DET_MAX_BLOCKS 4096                                       // loss / MSE / GAE workgroups per launch (rows <= 1 M)
 #define DET_LOSS_W (4 + 2 * GO1PPO_MAX_ACTIONS)
 #define GO1PPO_HEAD 64                                            // padded head width of the policy (fused.py HEAD): npv <= 64
@@ -200,28 +210,45 @@ __global__ __launch_bounds__(256) void elu_bwd_tile_kernel(const bf16_t* d, int 
 __device__ float det_loss_slab[DET_MAX_BLOCKS * DET_LOSS_W];
 __device__ float det_mse_slab[DET_MAX_BLOCKS * DET_MSE_W];
 __device__ double det_gae_slab[DET_MAX_BLOCKS * 2];
-__device__ float det_tn_slab[DET_TN_MAXP * DET_TN_MAXNT * DET_TN_MAXS * DET_TN_W];
+__device__ __attribute__((aligned(16))) float det_tn_slab[DET_TN_MAXP * DET_TN_MAXNT * DET_TN_MAXS * DET_TN_W];
 __device__ unsigned det_count[3 + DET_TN_MAXP * DET_TN_MAXNT];  // [0] loss, [1] MSE, [2] GAE, [3 + p * MAXNT + tile] TN bias
 enum { DET_LOSS = 0, DET_MSE = 1, DET_GAE = 2, DET_TN = 3 };
 
-// after this workgroup's slab stores: true in the last of `parts` contributors (all of whose stores it then sees)
+// one slab value, written through to memory (global_store_dword / _dwordx2 ... sc1)
+__device__ __forceinline__ void det_put(float* p, float x) {
+  __hip_atomic_store((__attribute__((address_space(1))) float*)p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void det_put(double* p, double x) {
+  __hip_atomic_store((__attribute__((address_space(1))) double*)p, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// four values of a weight-gradient bias slab row, written through (buffer_store_dwordx4 ... sc1); `row` is the row's start and `off`
+// a byte offset into it (a multiple of 16): a store past the row's DET_TN_W values is dropped by the buffer's range check
+__device__ __forceinline__ void det_put4(float* row, int off, f32x4 v) {
+  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(row, 0, DET_TN_W * (int)sizeof(float), 0x00020000);
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, v), rsrc, off, 0, 16 /* sc1 */);
+}
+
+// after this workgroup's det_put / det_put4 stores (all of them, from any wave): true in the last of `parts` contributors, which then
+// sees every contributor's row through plain loads
 __device__ __forceinline__ bool det_last(unsigned* counter, unsigned parts) {
   __shared__ unsigned s_last;
-  __threadfence();                                               // release: this workgroup's slab row, device-wide
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // every wave: its write-through slab stores have reached memory
   __syncthreads();
   if (threadIdx.x == 0) {
-    const unsigned t = atomicAdd(counter, 1u);
+    const unsigned t = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     s_last = t == parts - 1;
-    if (s_last) atomicExch(counter, 0u);                         // every contributor has counted: ready for the next launch
+    if (s_last) {
+      __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // every contributor has counted: ready for the next launch
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");        // acquire: the other rows (this CU's L1 drops its copies)
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the barrier below then waits for the invalidate
+    }
   }
   __syncthreads();
-  const bool last = s_last;
-  if (last) __threadfence();                                     // acquire: the other rows
-  return last;
+  return s_last;
 }
 
 // ---------------------------------------------------------------------------------------------- block reduction helper
-// the workgroup's sums of v[i] are STORED to dst[i] (a slab row; null: not needed)
+// the workgroup's sums of v[i] are STORED to dst[i] (a slab row, written through for det_last; null: not needed)
 template <int NV>
 __device__ __forceinline__ void block_reduce_store(float (&v)[NV], float* const (&dst)[NV], float* lds /* [4][NV] */) {
 #pragma unroll
@@ -238,7 +265,7 @@ __device__ __forceinline__ void block_reduce_store(float (&v)[NV], float* const 
   if (threadIdx.x < NV) {
     float t = 0.f;
     for (int w = 0; w < (int)(blockDim.x >> 6); w++) t += lds[w * NV + threadIdx.x];
-    if (dst[threadIdx.x]) *dst[threadIdx.x] = t;
+    if (dst[threadIdx.x]) det_put(dst[threadIdx.x], t);
   }
 }
 
@@ -631,7 +658,7 @@ __global__ __launch_bounds__(256) void gae_kernel(const float* rewards, const ui
   for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); }
   if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s1; red[1][threadIdx.x >> 6] = s2; }
   __syncthreads();
-  if (threadIdx.x < 2) det_gae_slab[(int64_t)blockIdx.x * 2 + threadIdx.x] = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+  if (threadIdx.x < 2) det_put(det_gae_slab + (int64_t)blockIdx.x * 2 + threadIdx.x, red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3]);
   if (!det_last(&det_count[DET_GAE], gridDim.x)) return;
   if (threadIdx.x < 2) {
     double t = 0.0;
@@ -1116,8 +1143,9 @@ extern "C" int go1ppo_loss(const Go1PpoLossArgs* a, void* stream) {
   // (one wavefront per workgroup — 384 workgroups instead of 96 — measured 32 us against 22: four times the same-address atomics of the reductions)
   // (measured, round 6 — profiles/r06_loss_kernel_ablation.txt: the same-address atomics are 1 us of the kernel's 16-22; meeting the sums through
   //  per-workgroup rows and a last-workgroup ticket instead took 45 us: the device-scope fences in front of the ticket write the XCD's L2 back.
-  //  That is the form the kernel now has (det_last): the price of sums that come out the same in every run; fp32 atomics made the update —
-  //  and so every later rollout — differ from run to run.  Its cost in the update: profiles/det_sums_kernel_stats.txt)
+  //  Rows and ticket are the form the kernel now has (det_last): sums that come out the same in every run; fp32 atomics made the update —
+  //  and so every later rollout — differ from run to run.  The rows are published write-through, without those fences:
+  //  profiles/det_publish_kernel_stats.txt)
   loss_kernel<<<dim3((unsigned)((a->rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(*a);
   return hipGetLastError() == hipSuccess ? 0 : -9;
 }

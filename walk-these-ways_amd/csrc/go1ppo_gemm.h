@@ -299,8 +299,10 @@ extern "C" int go1ppo_gemm_nt(const Go1PpoGemmArgs* a, void* stream) {
 //     (Go1PpoWgradProblem.partials, plain stores; summed in a fixed order by the optimiser's norm pass or go1ppo_grad_reduce) — or, without
 //     slabs, meet in fp32 atomics on the gradient buffer itself (~200 G atomic adds/s chip-wide: 15.6 of the 64.5 us of the PPO pass's
 //     launch, which is why the product path uses slabs); the bias gradient (column sums of dZ) is one more MFMA per fragment against a
-//     fragment of ones, in the workgroups of the first column tile, stored as the row chunk's row of a bias slab and summed in chunk
-//     order by the last of those workgroups (det_last, go1ppo.hip): the same bias gradient in every run.
+//     fragment of ones, in the workgroups of the first column tile, stored write-through (16-B sc1 stores) as the row chunk's row of a
+//     bias slab and summed in chunk order by the last of those workgroups (det_last, go1ppo.hip): the same bias gradient in every run.
+//     No release fence: it would write back the whole XCD L2, the weight-slab tiles included, which stay plain stores (the next
+//     kernel reads them, and the kernel boundary orders them).
 // rows % 64 == 0, n % 8 == 0, k % 8 == 0.
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;
 typedef __attribute__((ext_vector_type(8))) short s16x8_t;
@@ -346,7 +348,7 @@ __device__ __forceinline__ bf16x8_t tn_operand(const TnFrags& f, int i) {
 #define WTN_THREADS 512
 
 __device__ __forceinline__ void wgrad_tn_body(const bf16_t* P, int ldp, const bf16_t* Q, int ldq, int64_t m_begin, int steps,
-                                              float* C, int ldc, float* bias_grad, int N, int K, int n0, int k0,
+                                              float* C, int ldc, float* bias_row, int N, int K, int n0, int k0,
                                               bf16_t (*lds)[2][WTN_STEP * WTN_T], int zero_n, int zero_k0, int zero_k1, bool slab) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   // ---- staging: wave w moves row blocks (4 rows of 256 B each) 2w, 2w+1 of both operand tiles
@@ -391,7 +393,7 @@ __device__ __forceinline__ void wgrad_tn_body(const bf16_t* P, int ldp, const bf
 #pragma unroll
     for (int b = 0; b < 2; b++) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
-  const bool do_bias = bias_grad && k0 == 0 && wk == 0;
+  const bool do_bias = bias_row && k0 == 0 && wk == 0;
   const s16x8_t ones_bits = {0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80};
   const bf16x8_t ones = __builtin_bit_cast(bf16x8_t, ones_bits);
 
@@ -460,8 +462,10 @@ __device__ __forceinline__ void wgrad_tn_body(const bf16_t* P, int ldp, const bf
           else atomicAdd(C + (int64_t)n * ldc + k, acc[a][b][e]);
         }
       }
-      if (do_bias && i16 == 0) bias_grad[n] = bacc[a][e];       // this row chunk's row of the bias slab (wgrad_tn_batched_kernel)
     }
+    // this row chunk's row of the bias slab (wgrad_tn_batched_kernel, indexed by n - n0): lane i16 == 0 holds 4 consecutive columns
+    // (n % 8 == 0: all of them or none in range), stored as one 16-B write-through store for det_last (go1ppo.hip)
+    if (do_bias && i16 == 0 && n0 + wn * 64 + a * 16 + 4 * g < N) det_put4(bias_row, (wn * 64 + a * 16 + 4 * g) * (int)sizeof(float), bacc[a]);
   }
 }
 
@@ -497,7 +501,7 @@ __device__ __forceinline__ bf16x8_t tnw_operand(const TnFragsW& f, int i) {
 }
 
 __device__ __forceinline__ void wgrad_tn_body_wide(const bf16_t* P, int ldp, const bf16_t* Q, int ldq, int64_t m_begin, int steps,
-                                                   float* C, int ldc, float* bias_grad, int N, int K, int n0, int k0, char* lds,
+                                                   float* C, int ldc, float* bias_row, int N, int K, int n0, int k0, char* lds,
                                                    int zero_n, int zero_k0, int zero_k1, bool slab) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   // ---- staging: 32 row blocks (4 rows of 256 B) of the two dZ images + 16 of the H image per step; wave w moves dZ blocks 4w .. 4w+3
@@ -536,7 +540,7 @@ __device__ __forceinline__ void wgrad_tn_body_wide(const bf16_t* P, int ldp, con
 #pragma unroll
     for (int b = 0; b < 4; b++) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
-  const bool do_bias = bias_grad && k0 == 0 && wk == 0;
+  const bool do_bias = bias_row && k0 == 0 && wk == 0;
   const s16x8_t ones_bits = {0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80};
   const bf16x8_t ones = __builtin_bit_cast(bf16x8_t, ones_bits);
   const uint32_t lds0 = (uint32_t)(uintptr_t)(lds_void_t*)lds;
@@ -602,8 +606,10 @@ __device__ __forceinline__ void wgrad_tn_body_wide(const bf16_t* P, int ldp, con
           else atomicAdd(C + (int64_t)n * ldc + k, acc[a][b][e]);
         }
       }
-      if (do_bias && i16 == 0) bias_grad[n] = bacc[a][e];       // this row chunk's row of the bias slab (wgrad_tn_batched_kernel)
     }
+    // this row chunk's row of the bias slab (wgrad_tn_batched_kernel, indexed by n - n0): lane i16 == 0 holds 4 consecutive columns
+    // (n % 8 == 0: all of them or none in range), stored as one 16-B write-through store for det_last (go1ppo.hip)
+    if (do_bias && i16 == 0 && n0 + wn * 64 + a * 16 + 4 * g < N) det_put4(bias_row, (wn * 64 + a * 16 + 4 * g) * (int)sizeof(float), bacc[a]);
   }
 }
 // the tile shape of a problem: 256 x 128 when n is a multiple of 256 AND the partial tiles go to slabs, 128 x 128 otherwise (kernel and
@@ -634,11 +640,11 @@ __global__ __launch_bounds__(WTN_THREADS, 1) void wgrad_tn_batched_kernel(const 
   const bool slab = P.partials != nullptr;
   float* C = slab ? P.partials + (int64_t)split * P.partial_stride : P.dW;
   const int steps = (int)((m_end - m_begin) / WTN_STEP);
-  // bias: the workgroups of the first column tile store their column sums as row `split` of the (problem, n tile) bias slab, indexed by n
+  // bias: the workgroups of the first column tile store their column sums as row `split` of the (problem, n tile) bias slab, indexed by n - n0
   const int nt = tile / tiles_k, n0 = nt * (wide ? 2 * WTN_T : WTN_T);
   const bool bias = P.bias_grad != nullptr && tile % tiles_k == 0;
   float* bias_slab = det_tn_slab + (int64_t)(p * DET_TN_MAXNT + nt) * DET_TN_MAXS * DET_TN_W;
-  float* bias_row = bias ? bias_slab + (int64_t)split * DET_TN_W - n0 : nullptr;
+  float* bias_row = bias ? bias_slab + (int64_t)split * DET_TN_W : nullptr;
   if (wide)
     wgrad_tn_body_wide((const bf16_t*)P.dz, P.ld_dz, (const bf16_t*)P.h, P.ld_h, m_begin, steps, C, P.ldw, bias_row, P.n, P.k,
                        n0, (tile % tiles_k) * WTN_T, lds_raw, P.zero_n, P.zero_k0, P.zero_k1, slab);
