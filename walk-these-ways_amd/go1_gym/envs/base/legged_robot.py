@@ -145,6 +145,8 @@ class LeggedRobot(BaseTask):
         self.debug_viz = False
         self.init_done = False
         self.initial_dynamics_dict = initial_dynamics_dict
+        self._render = None               # go1render_host.Go1Render, created by the first start_recording() / render()
+        self._frames = [[], []]           # per camera: the last complete recording handed out
         if eval_cfg is not None:          # reference legged_robot.py:41-42
             self._parse_cfg(eval_cfg)
         self._parse_cfg(cfg)
@@ -424,6 +426,7 @@ class LeggedRobot(BaseTask):
         if not actions.is_contiguous():
             actions = actions.contiguous()
         self.sim.step(actions)
+        self._record_step()
         if self._curriculum_sync and (self.common_step_counter + 1) % self.sim_config.curriculum_update_interval == 0:
             # ONE exchange for the last `curriculum_update_interval` steps' success counts (a slot per step), then the per-step
             # updates in order: every rank applies what a single process over the concatenated shards would
@@ -452,10 +455,13 @@ class LeggedRobot(BaseTask):
         """reference legged_robot.py:150-239."""
         if len(env_ids) == 0:
             return
-        if len(env_ids) == self.num_envs:
+        full = len(env_ids) == self.num_envs
+        if full:
             self.sim.reset_idx(None)
         else:
             self.sim.reset_idx(torch.as_tensor(env_ids, device=self.device))
+        if self._render is not None and self._render.any_armed:     # a reset of the recorded env ends or starts a recording (:1003-1015)
+            self._render.note_reset(None if full else env_ids)
 
     def set_idx_pose(self, env_ids, dof_pos, base_state):
         """reference legged_robot.py:241-261: the buffers ARE the simulator state, so writing them is the push."""
@@ -490,24 +496,72 @@ class LeggedRobot(BaseTask):
         cdf = np.cumsum(w.astype(np.float64), axis=1)
         self.buffers.curriculum_cdf.copy_(torch.from_numpy((cdf / cdf[:, -1:]).astype(np.float32)))
 
-    # ---- recording: no renderer on this stack; the Runner calls these every iteration ------------------
+    # ---- recording (reference legged_robot.py:1591-1673): libgo1render draws the recorded env on the device -----------------
+    # Camera 0 records train env 0, camera 1 the first evaluation env (reference :1600-1604).  The state of a recording lives in
+    # a device control block (include/go1render.h): step() enqueues two launches while a camera is armed and none otherwise;
+    # get_complete_frames() reads the state once per call.  No-op (as the reference without a camera sensor) when
+    # cfg.env.record_video is off, when the simulator's buffers are not on a GPU, and on data-parallel ranks that do not hold
+    # global env 0 (one video per run).
+    def _renderer(self):
+        if self._render is None:
+            import go1render_host
+            self._render = go1render_host.Go1Render(self.sim_config, self.buffers, num_cameras=2 if self.num_eval_envs > 0 else 1)
+        return self._render
+
+    def _can_record(self):
+        return bool(self.cfg.env.record_video) and self.buffers.device.type == "cuda" and int(self.sim_config.env_id_offset) == 0
+
+    def _record_step(self):
+        if self._render is not None and self._render.any_armed:
+            self._render.record()
+
+    def _start(self, cam, env):
+        self._frames[cam] = []
+        if self._can_record():
+            # a recording spans at most the episode between two resets (max_episode_length + 1 steps): the ring never fills
+            self._renderer().arm(cam, env, int(self.max_episode_length) + 2)
+
+    def _pause(self, cam):
+        self._frames[cam] = []
+        if self._render is not None and cam < len(self._render.armed):
+            self._render.disarm(cam)
+
+    def _complete(self, cam):
+        rec = self._render
+        if rec is not None and cam < len(rec.armed) and rec.armed[cam]:
+            frames = rec.complete_frames(cam)
+            if frames is not None:
+                self._frames[cam] = frames
+        return self._frames[cam]
+
     def start_recording(self):
         self.record_now = True
+        self._start(0, 0)
 
     def start_recording_eval(self):
         self.record_eval_now = True
+        if self.num_eval_envs > 0:
+            self._start(1, self.num_train_envs)
 
     def pause_recording(self):
         self.record_now = False
+        self._pause(0)
 
     def pause_recording_eval(self):
         self.record_eval_now = False
+        self._pause(1)
 
     def get_complete_frames(self):
-        return []
+        """[] until the recording started by start_recording() is complete, then its frames ((240, 360, 4) uint8 RGBA arrays)
+        until pause_recording() / start_recording()"""
+        return self._complete(0)
 
     def get_complete_frames_eval(self):
-        return []
+        return self._complete(1)
 
     def render(self, mode="rgb_array"):
-        raise NotImplementedError("no renderer on the MI355X stack (SURVEY.md §5 video: out of scope)")
+        """reference :1612-1620: env 0 from its recording camera, now: (240, 360, 4) uint8 RGBA"""
+        assert mode == "rgb_array"
+        if self.buffers.device.type != "cuda":
+            raise NotImplementedError("render(): the renderer is a HIP library; this simulator's buffers are not on a GPU")
+        return self._renderer().image(0).cpu().numpy()

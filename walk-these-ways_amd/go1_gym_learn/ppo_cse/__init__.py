@@ -187,6 +187,11 @@ class Runner:
         if len(frames) > 0:
             self.env.pause_recording()
             logger.save_video(frames, f"videos/{it:05d}.mp4", fps=1 / self.env.dt)
+        if self.env.num_eval_envs > 0:
+            frames = self.env.get_complete_frames_eval()
+            if len(frames) > 0:
+                self.env.pause_recording_eval()
+                logger.save_video(frames, f"videos/{it:05d}_eval.mp4", fps=1 / self.env.dt)
 
     def get_inference_policy(self, device=None):
         self.alg.sync_module()

@@ -139,7 +139,62 @@ class _Logger:
         shutil.copyfile(file_path, dst)
 
     def save_video(self, frames, path, fps=30):
-        pass          # no renderer on this stack (SURVEY.md §5 "video")
+        """Write `frames` ((H, W, 3 or 4) uint8 arrays) as an animated PNG at `path` with its suffix replaced by .png (no mp4 encoder
+        offline; browsers play APNG).  Encoded on a background (non-daemon) thread, which is returned: join() it to wait for the file."""
+        import threading
+        import numpy as np
+        frames = [np.asarray(f) for f in frames]
+        p = os.path.splitext(self._path(path))[0] + ".png"
+        os.makedirs(os.path.dirname(p), exist_ok=True)
+        t = threading.Thread(target=write_apng, args=(p, frames, fps), name="save_video", daemon=False)
+        t.start()
+        return t
+
+
+def _chunk(kind, data):
+    import struct
+    import zlib
+    return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)
+
+
+def write_apng(path, frames, fps, level=6):
+    """Animated PNG (APNG) with zlib and struct only: signature, IHDR, acTL, then per frame fcTL (delay 1/fps as a fraction) and
+    IDAT (first frame) or fdAT (the others) with one shared sequence number, IEND.  8-bit RGBA (RGB frames get alpha 255), every
+    frame full size, filter type 0 on every row."""
+    import struct
+    import zlib
+    from fractions import Fraction
+    import numpy as np
+    if len(frames) == 0:
+        raise ValueError("save_video: no frames")
+    h, w = frames[0].shape[:2]
+    sec = 1.0 / float(fps)
+    delay = Fraction(sec).limit_denominator(max(1, min(65535, int(65535 / max(sec, 1.0)))))      # both terms fit 16 bits
+    num, den = delay.numerator, delay.denominator
+    out = [b"\x89PNG\r\n\x1a\n", _chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 6, 0, 0, 0)),
+           _chunk(b"acTL", struct.pack(">II", len(frames), 0))]
+    seq = 0
+    for i, f in enumerate(frames):
+        f = np.ascontiguousarray(f, dtype=np.uint8)
+        if f.shape[:2] != (h, w):
+            raise ValueError(f"save_video: frame {i} is {f.shape[:2]}, frame 0 is {(h, w)}")
+        if f.ndim == 3 and f.shape[2] == 3:
+            f = np.concatenate([f, np.full((h, w, 1), 255, np.uint8)], axis=2)
+        raw = np.zeros((h, 1 + 4 * w), np.uint8)          # filter byte 0, then the row
+        raw[:, 1:] = f.reshape(h, 4 * w)
+        data = zlib.compress(raw.tobytes(), level)
+        out.append(_chunk(b"fcTL", struct.pack(">IIIIIHHBB", seq, w, h, 0, 0, num, den, 0, 0)))
+        seq += 1
+        if i == 0:
+            out.append(_chunk(b"IDAT", data))
+        else:
+            out.append(_chunk(b"fdAT", struct.pack(">I", seq) + data))
+            seq += 1
+    out.append(_chunk(b"IEND", b""))
+    tmp = path + ".part"
+    with open(tmp, "wb") as fh:
+        fh.writelines(out)
+    os.replace(tmp, path)
 
 
 logger = _Logger()
