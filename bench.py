@@ -12,9 +12,16 @@ domain randomisation, device command curriculum), bf16 policy.  Synthetic: rando
 loop, initial states from the reset distribution.  N > 1: every rank owns 4096 envs (weak scaling), gradients are
 all-reduced over RCCL; value = total env-steps of all ranks / max-over-ranks time.
 
-Extra JSON objects: `roofline` (step kernel's algorithmic HBM bytes / per-launch HIP-event duration, DESIGN.md
-"Measurement") and, on rank 0 at N=1, `cpu_baseline` (the fp64 oracle restatement of the same env step on the
-host cores — the reference's own CPU path, Isaac Gym CPU-PhysX, is a closed binary that cannot run here).
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line.  Beside the headline it
+carries only what the timed steps themselves give: `roofline` (step kernel's algorithmic HBM bytes / per-launch HIP-event
+duration of the timed launches, traffic from the committed PMC passes, DESIGN.md "Measurement") and `guard_activations`.
+
+--full adds, at N=1 and after the headline's outputs are written: the step kernel's HBM traffic measured live (two
+rocprofv3 passes), `long_window` (200 more iterations), the extra records (sim-only and sim + inference rates,
+`update_roofline`, `dropin_default`, `rough_trimesh`, `envs_8192`), `reference_python_maps_cpu` (the committed timing of
+the reference's tensor maps) and `cpu_baseline` (the fp64 oracle restatement of the same env step on the host cores —
+the reference's own CPU path, Isaac Gym CPU-PhysX, is a closed binary that cannot run here).  --headline-only,
+--no-traffic and --no-cpu-baseline leave parts of that out.
 """
 import argparse
 import json
@@ -434,7 +441,10 @@ def main():
     ap.add_argument("--envs", type=int, default=4096, help="environments per GPU")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--fp32", action="store_true", help="fp32 policy instead of bf16 autocast")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run every other measurement (N=1): live HBM traffic of the step "
+                    "kernel, the 200-iteration window, sim-only / inference rates, update roofline, drop-in train.py, rough terrain, 8192 envs, "
+                    "the committed reference timing and the CPU baseline; a plain run does only the headline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--sim-only", action="store_true", help="diagnostic: time env.step alone with pre-generated actions")
     ap.add_argument("--zero-actions", action="store_true", help="diagnostic with --sim-only: standing robots (few resets)")
     ap.add_argument("--rollout-only", action="store_true", help="diagnostic: sim + policy inference + storage, no update (SURVEY 8d metric 2)")
@@ -445,9 +455,10 @@ def main():
     ap.add_argument("--rough", action="store_true", help="diagnostic: BASELINE configs[2] (trimesh tile grid + height scan) instead of the flat headline "
                     "configuration — with --sim-only for profiles of go1_step_kernel_walls; never the headline line")
     ap.add_argument("--breakdown", action="store_true", help="diagnostic: print rollout/update split to stderr (adds syncs)")
-    ap.add_argument("--headline-only", action="store_true", help="skip the extra single-GPU records (rates, height field, 8192 envs)")
-    ap.add_argument("--no-traffic", action="store_true", help="do not run the two rocprofv3 --pmc passes that measure the step kernel's HBM traffic "
-                                                              "(roofline.traffic then comes from the committed passes in profiles/)")
+    ap.add_argument("--headline-only", action="store_true", help="with --full: skip the live traffic passes, the 200-iteration window and the extra "
+                                                                 "single-GPU records (rates, height field, 8192 envs)")
+    ap.add_argument("--no-traffic", action="store_true", help="with --full: do not run the two rocprofv3 --pmc passes that measure the step kernel's "
+                                                              "HBM traffic (roofline.traffic then comes from the committed passes in profiles/, as in a plain run)")
     ap.add_argument("--curriculum-interval", type=int, default=1,
                     help="commands.curriculum_update_interval K: 1 = the reference's per-step curriculum update (curriculum.py) at EVERY rank count, so "
                          "that the 1-GPU headline and the N-GPU scaling numbers run the same algorithm; K > 1 coalesces the sharded run's "
@@ -610,7 +621,7 @@ def main():
                 break
             except (OSError, KeyError, ValueError):
                 continue
-        if world == 1 and not args.no_traffic and not args.headline_only and not (args.sim_only or args.rollout_only) and args.envs == 4096:
+        if args.full and world == 1 and not args.no_traffic and not args.headline_only and not (args.sim_only or args.rollout_only) and args.envs == 4096:
             measured, how = measure_step_kernel_traffic(args.envs)
             if measured is not None:
                 traffic, traffic_src = measured, how
@@ -654,19 +665,20 @@ def main():
         out["guard_activations"] = {"fatal": faults["fatal"], "by_site": {k: v for k, v in faults.items() if k != "fatal" and v},
                                     "env_steps": args.envs * T * (args.steps + args.warmup),
                                     "note": "containments of failed environments (include/go1sim.h Go1FaultBit) during warm-up + timed steps"}
-        if world == 1 and not args.headline_only and not (args.sim_only or args.rollout_only):
+        if args.full and world == 1 and not args.headline_only and not (args.sim_only or args.rollout_only):
             # the driver times --steps 20 (0.45 s): the same measurement over a 200-iteration window next to it
             long_iters = 200
             rate, obs_dict = time_iterations(runner, env, obs_dict, long_iters, warmup=0)
             out["long_window"] = {"iterations": long_iters, "value": rate, "ms_per_step": 1e3 * args.envs * T / rate, "unit": "env-steps/s",
                                   "note": "same workload and code path as `value`, timed over 200 PPO iterations in one window"}
             out.update(extra_records(args, env, runner, obs_dict, device))
-        try:
-            with open(os.path.join(REPO, "profiles", "reference_python_maps_cpu.json")) as f:
-                out["reference_python_maps_cpu"] = json.load(f)       # produced where /root/reference exists (tools/time_reference_maps.py)
-        except (OSError, ValueError):
-            out["reference_python_maps_cpu"] = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            try:
+                with open(os.path.join(REPO, "profiles", "reference_python_maps_cpu.json")) as f:
+                    out["reference_python_maps_cpu"] = json.load(f)   # produced where the reference is checked out (tools/time_reference_maps.py)
+            except (OSError, ValueError):
+                out["reference_python_maps_cpu"] = None
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.envs)
         print(json.dumps(out))
     if use_dist:

@@ -550,3 +550,37 @@ def test_rccl_one_rank_bench_runs_the_data_parallel_path(extra):
     assert t["all_reduce"] > 0 and t["curriculum_all_reduce"] > 0
     if "--zero1" in extra:
         assert t["reduce_scatter"] > 0 and t["all_gather"] > 0
+
+
+def test_plain_bench_runs_only_the_headline(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: set-up, warm-up, the timed steps, --dump-outputs and the line — none
+    of the records --full adds (live traffic passes, 200-iteration window, other configurations, reference timing, CPU baseline), and
+    at most 30 s of the process's wall time outside its warm-up and timed steps."""
+    import json
+    import subprocess
+    import sys
+    import time
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    steps, warmup = 5, 3
+    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+           "--dump-outputs", str(tmp_path / "out")]
+    env = {k: v for k, v in os.environ.items() if k != "PYTORCH_TUNABLEOP_ENABLED"}    # the shipped GEMM table, as a plain run has it
+    t0 = time.perf_counter()
+    r = subprocess.run(cmd, cwd=repo, env=env, capture_output=True, text=True, timeout=300)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec["metric"] == "env-steps/sec (sim+PPO)" and rec["unit"] == "env-steps/s" and rec["higher_is_better"] is True
+    assert rec["dtype"] == "f32" and rec["steps"] == steps and rec["warmup"] == warmup and rec["n_gpus"] == 1
+    assert rec["value"] == pytest.approx(4096 * 24 / (rec["ms_per_step"] * 1e-3), rel=1e-6)
+    assert rec["roofline"]["launches"] == 24 * steps and rec["roofline"]["traffic_source"].startswith("profiles/")
+    full_only = {"long_window", "rates", "update_roofline", "dropin_default", "rough_trimesh", "envs_8192", "reference_python_maps_cpu",
+                 "cpu_baseline"}
+    assert not full_only & set(rec), sorted(full_only & set(rec))
+    assert sorted(os.listdir(tmp_path / "out")) == sorted(f"{k}.npy" for k in (
+        "obs", "privileged_obs", "obs_history", "actions", "rewards", "dones", "values", "actions_log_prob", "returns", "advantages",
+        "weights", "losses", "env_index"))
+    outside = wall - (steps + warmup) * rec["ms_per_step"] * 1e-3
+    assert outside < 30.0, f"{outside:.1f} s outside the warm-up and timed steps"
