@@ -15,6 +15,9 @@
  *     Arrays documented as (N,K) are row-major per environment (consumed by GEMMs).
  *   - quaternions are xyzw (go1_gym/envs/base/legged_robot_config.py:203).
  *   - all arithmetic is fp32 on device (reference: torch default / Isaac Gym float32 tensors).
+ *   - the torque model of control_type 1 (the actuator network) is a run-time input: go1sim_create installs the
+ *     network the library was built with (csrc/go1_actuator_data.h, the reference's unitree_go1.pt), and
+ *     go1sim_set_actuator_net replaces it with another 6 -> 32 -> 32 -> 1 softsign network (struct Go1ActuatorTable).
  */
 #ifndef GO1SIM_H
 #define GO1SIM_H
@@ -339,6 +342,23 @@ typedef struct Go1SimBuffers {
   float* measured_heights;         /* [num_height_x*num_height_y][N] or NULL */
 } Go1SimBuffers;
 
+/* The actuator network of control_type 1 (reference legged_robot.py:1238-1253, scripts/actuator_net/utils.py:66-72,93):
+ *   torque = W2 . softsign(W1 softsign(W0 x + B0) + B1) + B2,   softsign(v) = v / (1 + |v|),
+ *   x = (pos_err, pos_err_last, pos_err_last_last, vel, vel_last, vel_last_last) of one joint (legged_robot.py:927-937).
+ * Weights are (out, in), as torch.nn.Linear stores them.  go1sim_set_actuator_net / _get_actuator_net exchange the table as
+ * GO1_ACT_TABLE_FLOATS floats in this field order.  One table per handle: train and evaluation environments share it. */
+#define GO1_ACT_INPUTS 6
+#define GO1_ACT_HIDDEN 32
+#define GO1_ACT_TABLE_FLOATS 1313   /* 32*6 + 32 + 32*32 + 32 + 32 + 1 */
+struct Go1ActuatorTable {
+  float W0[GO1_ACT_HIDDEN][GO1_ACT_INPUTS];
+  float B0[GO1_ACT_HIDDEN];
+  float W1[GO1_ACT_HIDDEN][GO1_ACT_HIDDEN];
+  float B1[GO1_ACT_HIDDEN];
+  float W2[GO1_ACT_HIDDEN];
+  float B2;
+};
+
 typedef struct Go1Sim Go1Sim;      /* opaque handle */
 
 /* Create a simulator instance bound to caller-owned device buffers.
@@ -358,6 +378,15 @@ int go1sim_set_config(Go1Sim* sim, const Go1SimConfig* cfg);
  * rewards and command distribution: the caller copies those from the train configuration); the kernels select the block
  * per wavefront, so num_train_envs must be a multiple of 16 (-3 otherwise).  num_train_envs == num_envs: no split. */
 int go1sim_set_eval_config(Go1Sim* sim, const Go1SimConfig* eval_cfg, int32_t num_train_envs);
+
+/* Actuator network (struct Go1ActuatorTable): `table` is a HOST array of GO1_ACT_TABLE_FLOATS floats, or NULL to restore the
+ * built-in network.  Blocking copy, like go1sim_set_config; it holds for every environment, train and evaluation alike, and
+ * survives later go1sim_set_config / go1sim_set_eval_config calls.  The |W1| entries must lie within 65504 (the matrix-core
+ * path splits W1 into fp16 hi + lo) and every entry must be finite: -7 otherwise, and the table in force is kept.
+ * Replaces: torch.jit.load(actuator_network_path) (legged_robot.py:1238-1240). */
+int go1sim_set_actuator_net(Go1Sim* sim, const float* table);
+/* Copy the table in force into the host array `out` (GO1_ACT_TABLE_FLOATS floats). */
+int go1sim_get_actuator_net(Go1Sim* sim, float* out);
 
 /* One policy step for all environments: clip actions, `decimation` x {torque model, physics substep},
  * derived state, gait clock, command resampling, DR cadence, termination, rewards, in-kernel reset,

@@ -17,7 +17,6 @@
 #define GO1_CONST static __device__ __constant__ const
 #define GO1_REAL float
 #include "go1_model_data.h"
-#include "go1_actuator_data.h"
 
 #define WAVE 64
 #define EPW 16                       // environments per wavefront
@@ -96,30 +95,35 @@ struct SolverLds {
 // ================================================================================================
 DEV float softsign(float x) { return x * __builtin_amdgcn_rcpf(1.f + fabsf(x)); }   // v_rcp_f32: <= 1 ulp
 
+// The actuator network's weights (include/go1sim.h Go1ActuatorTable) sit in the handle's constant block (go1sim.hip SimConst):
+// installed at go1sim_create, replaced by go1sim_set_actuator_net.  Read through the constant address space: wave-uniform
+// indices become scalar loads.
+typedef const GO1_CONSTANT Go1ActuatorTable& ActRef;
+
 // 6->32->32->1 actuator network for the three joints of one leg: every weight (wave-uniform, scalar loads from
 // constant memory) feeds 3 independent accumulation chains, hiding the dependent-FMA latency of a single chain.
-DEV void actuator_net3(const float in[3][6], float out[3]) {
+DEV void actuator_net3(ActRef act, const float in[3][6], float out[3]) {
   float h0[3][32];
 #pragma unroll
   for (int i = 0; i < 32; i++) {
-    float a0 = GO1_ACT_B0[i], a1 = a0, a2 = a0;
+    float a0 = act.B0[i], a1 = a0, a2 = a0;
 #pragma unroll
     for (int k = 0; k < 6; k++) {
-      const float w = GO1_ACT_W0[i][k];
+      const float w = act.W0[i][k];
       a0 = fmaf(w, in[0][k], a0); a1 = fmaf(w, in[1][k], a1); a2 = fmaf(w, in[2][k], a2);
     }
     h0[0][i] = softsign(a0); h0[1][i] = softsign(a1); h0[2][i] = softsign(a2);
   }
-  float o0 = GO1_ACT_B2, o1 = o0, o2 = o0;
+  float o0 = act.B2, o1 = o0, o2 = o0;
 #pragma unroll 2
   for (int i = 0; i < 32; i++) {
-    float a0 = GO1_ACT_B1[i], a1 = a0, a2 = a0;
+    float a0 = act.B1[i], a1 = a0, a2 = a0;
 #pragma unroll
     for (int k = 0; k < 32; k++) {
-      const float w = GO1_ACT_W1[i][k];
+      const float w = act.W1[i][k];
       a0 = fmaf(w, h0[0][k], a0); a1 = fmaf(w, h0[1][k], a1); a2 = fmaf(w, h0[2][k], a2);
     }
-    const float w2 = GO1_ACT_W2[i];
+    const float w2 = act.W2[i];
     o0 = fmaf(w2, softsign(a0), o0); o1 = fmaf(w2, softsign(a1), o1); o2 = fmaf(w2, softsign(a2), o2);
   }
   out[0] = o0; out[1] = o1; out[2] = o2;
@@ -142,19 +146,19 @@ typedef __attribute__((ext_vector_type(4))) float act_f32x4;
 enum { A_IN = 0, A_OUT = 192 * 8, A_IO_END = A_OUT + 4 * 192 };      // transient rows in / partial sums out: overlaid on the solver's matrix
 enum { A_W0 = 0, A_B1 = A_W0 + 32 * 8, A_W2 = A_B1 + 32, A_WF = A_W2 + 32, A_END = A_WF + 4 * 64 * 4 };      // constants of the launch
 
-DEV void actuator_lds_init(float* a, int lane) {          // once per launch, all 64 lanes
+DEV void actuator_lds_init(ActRef act, float* a, int lane) {          // once per launch, all 64 lanes
   for (int i = lane; i < 32 * 8; i += WAVE) {
     const int k = i >> 3, c = i & 7;
-    a[A_W0 + i] = c < 6 ? GO1_ACT_W0[k][c] : (c == 6 ? GO1_ACT_B0[k] : 0.f);
+    a[A_W0 + i] = c < 6 ? act.W0[k][c] : (c == 6 ? act.B0[k] : 0.f);
   }
-  if (lane < 32) { a[A_B1 + lane] = GO1_ACT_B1[lane]; a[A_W2 + lane] = GO1_ACT_W2[lane]; }
+  if (lane < 32) { a[A_B1 + lane] = act.B1[lane]; a[A_W2 + lane] = act.W2[lane]; }
   const int c = lane & 15, g = lane >> 4;
 #pragma unroll
   for (int i = 0; i < 2; i++) {
     act_f16x8 hi, lo;
 #pragma unroll
     for (int kk = 0; kk < 8; kk++) {
-      const float w = GO1_ACT_W1[16 * i + c][8 * g + kk];
+      const float w = act.W1[16 * i + c][8 * g + kk];
       const _Float16 h = (_Float16)w;
       hi[kk] = h;
       lo[kk] = (_Float16)(w - (float)h);
@@ -225,27 +229,27 @@ DEV void actuator_publish(float* io, int lane, const float in[3][6]) {       // 
     p[1] = (f4){in[jj][4], in[jj][5], 1.f, 0.f};
   }
 }
-DEV void actuator_collect(const float* io, int lane, float out[3]) {
+DEV void actuator_collect(ActRef act, const float* io, int lane, float out[3]) {
 #pragma unroll
   for (int jj = 0; jj < 3; jj++) {
     const int r = 3 * lane + jj;
-    out[jj] = ((io[A_OUT + r] + io[A_OUT + 192 + r]) + (io[A_OUT + 384 + r] + io[A_OUT + 576 + r])) + GO1_ACT_B2;
+    out[jj] = ((io[A_OUT + r] + io[A_OUT + 192 + r]) + (io[A_OUT + 384 + r] + io[A_OUT + 576 + r])) + act.B2;
   }
 }
 // Everything in one call (the piecewise entry points and workgroups of one wavefront): wave wv of nw takes tiles wv, wv + nw, ...
-DEV void actuator_net_mfma(float* a, float* io, int lane, int wv, int nw, bool master, const float in[3][6], float out[3]) {
+DEV void actuator_net_mfma(ActRef act, float* a, float* io, int lane, int wv, int nw, bool master, const float in[3][6], float out[3]) {
   if (master) actuator_publish(io, lane, in);
   BLOCK_SYNC(nw);
   actuator_tiles(a, io, lane, wv, nw);
   BLOCK_SYNC(nw);
-  if (master) actuator_collect(io, lane, out);
+  if (master) actuator_collect(act, io, lane, out);
 }
 
 struct Leg {             // the calling lane's leg
   float q[3], qd[3], tau[3];
 };
 
-DEV void compute_torques(CfgRef cfg, BufRef B, Leg& L, int leg, int e, int N, int head, float* act_lds, float* act_io, bool full_wave, int nw, uint32_t& fault) {
+DEV void compute_torques(CfgRef cfg, ActRef act, BufRef B, Leg& L, int leg, int e, int N, int head, float* act_lds, float* act_io, bool full_wave, int nw, uint32_t& fault) {
   const int nl = cfg.lag_timesteps + 1;
   const int h2 = (head + 1) % nl;
   float in[3][6], tq[3], tgt[3];
@@ -277,8 +281,8 @@ DEV void compute_torques(CfgRef cfg, BufRef B, Leg& L, int leg, int e, int N, in
       AT(B.joint_vel_last_last, j, e) = vl;
       AT(B.joint_vel_last, j, e) = L.qd[jj];
     }
-    if (full_wave) actuator_net_mfma(act_lds, act_io, (int)threadIdx.x & 63, 0, nw, true, in, tq);      // wave-uniform choice
-    else actuator_net3(in, tq);
+    if (full_wave) actuator_net_mfma(act, act_lds, act_io, (int)threadIdx.x & 63, 0, nw, true, in, tq);      // wave-uniform choice
+    else actuator_net3(act, in, tq);
   } else {
 #pragma unroll
     for (int jj = 0; jj < 3; jj++) {
@@ -391,9 +395,9 @@ DEV void torque_build_row(float* acth_, float* io, int hl, int sub) {
   p[1] = (f4){v1, v2, 1.f, 0.f};
   ACTH(AH_E2 + jj) = e1; ACTH(AH_E1 + jj) = err; ACTH(AH_V2 + jj) = v1; ACTH(AH_V1 + jj) = qd;
 }
-DEV void torque_collect(CfgRef cfg, Leg& L, const float* acth, const float* io, int lane, int leg, uint32_t& fault) {
+DEV void torque_collect(CfgRef cfg, ActRef act, Leg& L, const float* acth, const float* io, int lane, int leg, uint32_t& fault) {
   float tq[3];
-  actuator_collect(io, lane, tq);
+  actuator_collect(act, io, lane, tq);
 #pragma unroll
   for (int jj = 0; jj < 3; jj++) {
     float t = tq[jj] * ACTH(AH_MS + jj);
@@ -852,7 +856,7 @@ DEV float self_seg_radius(int seg) { return seg == 0 ? GO1_SELF_LEG_RADIUS : seg
 // PLANE: the terrain is the plane z = 0 (terrain_type 0; never with WALLS): no height samples, and the deepest corner of a box end
 // is known from the signs of the box axes' z components — one candidate per end instead of four
 template <bool WALLS, bool SIG, bool PLANE>
-DEV void physics_substep(CfgRef cfg, BufRef B, const SolverLds& Z, int lane, int nw, Base& s, Leg& L, V3 grav,
+DEV void physics_substep(CfgRef cfg, ActRef act, BufRef B, const SolverLds& Z, int lane, int nw, Base& s, Leg& L, V3 grav,
                          bool use_warm, float h, uint32_t& fault, uint32_t (&dropacc)[GO1_CC_COUNT], const float* acth, int e, int N, int sub PROF_PARAM) {
   float* const lds = Z.lds;
   lf4* const crl = Z.cr();
@@ -1261,7 +1265,7 @@ DEV void physics_substep(CfgRef cfg, BufRef B, const SolverLds& Z, int lane, int
   PROF(20);
   if (acth) {
     BLOCK_SYNC(nw);                       // the helpers' partial sums are in io[A_OUT]
-    torque_collect(cfg, L, acth, Z.act_io(), lane, leg, fault);
+    torque_collect(cfg, act, L, acth, Z.act_io(), lane, leg, fault);
   }
   // ---- ABA pass 2: calf -> thigh -> hip, then quad-sum into the base -------------------------------------------------------
   {

@@ -32,6 +32,10 @@
 #include "go1_math.h"
 #include "go1_maps.h"
 #include "go1_physics.h"
+// the built-in actuator network (the reference's unitree_go1.pt): HOST arrays, copied into every handle's table at go1sim_create
+#undef GO1_CONST
+#define GO1_CONST static const
+#include "go1_actuator_data.h"
 #define GO1SIM_STR_(x) #x
 #define GO1SIM_STR(x) GO1SIM_STR_(x)
 
@@ -44,7 +48,9 @@ struct SimConst {            // lives in device memory (one per handle): indexab
   int32_t num_train_envs;
   Go1SimBuffers buf;
   RewardPlan rew;            // derived at create / set_config: reward terms indexed by id (go1_maps.h)
+  Go1ActuatorTable act;      // the actuator network (control_type 1) of every environment: go1sim_set_actuator_net
 };
+static_assert(sizeof(Go1ActuatorTable) == GO1_ACT_TABLE_FLOATS * sizeof(float), "include/go1sim.h: the table is GO1_ACT_TABLE_FLOATS floats");
 // the wavefront's configuration block: 16 consecutive environments are all train or all evaluation environments
 #define WAVE_CFG(csc, first_env) (((first_env) >= (csc)->num_train_envs) ? (csc)->cfg_eval : (csc)->cfg)
 struct StepArgs {
@@ -119,7 +125,7 @@ DEV void step_body(const StepArgs& A, float* lds, lf4* ldsx, float* act_lds, flo
   const bool substep_only = A.mode == 2;                         // piecewise entry point: ONE physics substep with the torques in the buffer
   const bool mfma_torque = full_wave && cfg.control_type == 1 && !substep_only;
   const bool deferred = mfma_torque && nw == 4 && cfg.decimation <= ACT_MAX_DEC;     // torque model entirely on the helper wavefronts (3 x 64 lanes = the 192 rows)
-  if (mfma_torque && wv == 0) actuator_lds_init(act_lds, lane);
+  if (mfma_torque && wv == 0) actuator_lds_init(csc->act, act_lds, lane);
   reward_plan_to_lds(csc->rew, plan_lds, (int)threadIdx.x);
   PROF_INIT
   __syncthreads();
@@ -135,7 +141,7 @@ DEV void step_body(const StepArgs& A, float* lds, lf4* ldsx, float* act_lds, flo
         LDS_PHASE();                                      // rows 64 (wv - 1) .. + 63 = tiles 4 (wv - 1) .. + 3: built and consumed by this wavefront
         actuator_tiles(act_lds, Z.act_io(), lane, 4 * (wv - 1), 1, 4 * wv);
         BLOCK_SYNC(nw);                                   // (the master arrives here when it needs the torques)
-      } else if (mfma_torque) actuator_net_mfma(act_lds, Z.act_io(), lane, wv, nw, false, nullptr, nullptr);
+      } else if (mfma_torque) actuator_net_mfma(csc->act, act_lds, Z.act_io(), lane, wv, nw, false, nullptr, nullptr);
       BLOCK_SYNC(nw);                                     // the master's items and hand-over packets are in LDS
       emit_terrain_contacts(cfg, Z, lane >> 2, 4 * (wv - 1) + (lane & 3), 4 * (nw - 1), cfg.sim_dt);
       BLOCK_SYNC(nw);
@@ -230,10 +236,10 @@ DEV void step_body(const StepArgs& A, float* lds, lf4* ldsx, float* act_lds, flo
       torque_post_state(L, Z.act_io(), lane);
       PROF(22);
       BLOCK_SYNC(nw);
-    } else compute_torques(cfg, B, L, leg, e, N, head, act_lds, Z.act_io(), mfma_torque, nw, fault);
+    } else compute_torques(cfg, csc->act, B, L, leg, e, N, head, act_lds, Z.act_io(), mfma_torque, nw, fault);
     PROF(1);
     head = (head + 1) % nl;
-    physics_substep<WALLS, SIG, PLANE>(cfg, B, Z, lane, nw, s, L, grav, warm || (cfg.warm_start && sub > 0), h, fault, drops, deferred ? acth : nullptr, e, N, sub PROF_PASS);
+    physics_substep<WALLS, SIG, PLANE>(cfg, csc->act, B, Z, lane, nw, s, L, grav, warm || (cfg.warm_start && sub > 0), h, fault, drops, deferred ? acth : nullptr, e, N, sub PROF_PASS);
     PROF(30);
   };
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -296,7 +302,7 @@ extern "C" __global__ void __launch_bounds__(WAVE) go1_aux_kernel(const StepArgs
   const int lane = threadIdx.x, leg = lane & 3;
   const int e = blockIdx.x * EPW + (lane >> 2);
   const bool full_wave = (int)(blockIdx.x + 1) * EPW <= N;
-  if (A.mode == 1 && full_wave && cfg.control_type == 1) actuator_lds_init(act_lds, lane);
+  if (A.mode == 1 && full_wave && cfg.control_type == 1) actuator_lds_init(csc->act, act_lds, lane);
   if (e >= N) return;
   if (A.mode == 4) {       // tensor maps only
     PROF_DECL
@@ -315,7 +321,7 @@ extern "C" __global__ void __launch_bounds__(WAVE) go1_aux_kernel(const StepArgs
   if (A.mode == 1) {       // torques only (actions given as SoA)
 #pragma unroll
     for (int jj = 0; jj < 3; jj++) AT(B.actions, 3 * leg + jj, e) = AT(A.actions, 3 * leg + jj, e);
-    compute_torques(cfg, B, L, leg, e, N, A.lag_head, act_lds, act_io, full_wave, 1, fault);
+    compute_torques(cfg, csc->act, B, L, leg, e, N, A.lag_head, act_lds, act_io, full_wave, 1, fault);
     report_fault(B, e, fault);
     return;
   }
@@ -415,7 +421,8 @@ struct Go1Sim {
   int64_t counter;
   int32_t lag_head;
   int32_t history_slot;
-  SimConst* dconst;    // device copy of {cfg, buf}
+  Go1ActuatorTable act;
+  SimConst* dconst;    // device copy of {cfg, buf, act}
   int timing_cap;
   int64_t timing_n;
   hipEvent_t* ev;      // 2 * timing_cap
@@ -438,12 +445,22 @@ static int upload_const(Go1Sim* s) {
   const bool split = s->num_train > 0 && s->num_train < s->cfg.num_envs;
   h.cfg_eval = split ? s->cfg_eval : s->cfg;
   h.num_train_envs = split ? s->num_train : s->cfg.num_envs;
+  h.act = s->act;
   for (int id = 0; id < GO1_REW_COUNT; id++) { h.rew.kx_by_id[id] = -1; h.rew.scale_by_id[id] = 0.f; }
   for (int kx = 0; kx < s->cfg.num_rewards; kx++) {
     const int id = s->cfg.reward_ids[kx];
     if (id >= 0 && id < GO1_REW_COUNT) { h.rew.kx_by_id[id] = kx; h.rew.scale_by_id[id] = s->cfg.reward_scales[kx]; }
   }
   return hipMemcpy(s->dconst, &h, sizeof(SimConst), hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
+}
+
+static void builtin_actuator_net(Go1ActuatorTable& t) {
+  memcpy(t.W0, GO1_ACT_W0, sizeof(t.W0));
+  memcpy(t.B0, GO1_ACT_B0, sizeof(t.B0));
+  memcpy(t.W1, GO1_ACT_W1, sizeof(t.W1));
+  memcpy(t.B1, GO1_ACT_B1, sizeof(t.B1));
+  memcpy(t.W2, GO1_ACT_W2, sizeof(t.W2));
+  t.B2 = GO1_ACT_B2;
 }
 
 extern "C" int go1sim_create(const Go1SimConfig* cfg, const Go1SimBuffers* buffers, int device, Go1Sim** out) {
@@ -456,6 +473,7 @@ extern "C" int go1sim_create(const Go1SimConfig* cfg, const Go1SimBuffers* buffe
   s->cfg_eval = *cfg; s->num_train = cfg->num_envs;
   s->counter = 0; s->lag_head = 0; s->history_slot = 0; s->timing_cap = 0; s->timing_n = 0; s->ev = nullptr;
   s->dconst = nullptr;
+  builtin_actuator_net(s->act);
   if (hipMalloc((void**)&s->dconst, sizeof(SimConst)) != hipSuccess) { delete s; return -12; }
   if (upload_const(s) != 0) { (void)hipFree(s->dconst); delete s; return -13; }
   *out = s;
@@ -497,6 +515,27 @@ extern "C" int go1sim_set_eval_config(Go1Sim* s, const Go1SimConfig* cfg, int32_
   s->cfg_eval = *cfg;
   s->num_train = num_train_envs;
   return upload_const(s);
+}
+
+extern "C" int go1sim_set_actuator_net(Go1Sim* s, const float* table) {
+  if (!s) return -1;
+  Go1ActuatorTable t;
+  if (!table) builtin_actuator_net(t);
+  else {
+    memcpy(&t, table, sizeof(t));
+    for (int i = 0; i < GO1_ACT_TABLE_FLOATS; i++)
+      if (!(fabsf(table[i]) <= 3.0e38f)) return -7;
+    for (int i = 0; i < GO1_ACT_HIDDEN; i++)
+      for (int k = 0; k < GO1_ACT_HIDDEN; k++)
+        if (!(fabsf(t.W1[i][k]) <= 65504.f)) return -7;       // beyond fp16: the matrix-core path's hi / lo split of W1 would overflow
+  }
+  s->act = t;
+  return upload_const(s);
+}
+extern "C" int go1sim_get_actuator_net(Go1Sim* s, float* out) {
+  if (!s || !out) return -1;
+  memcpy(out, &s->act, sizeof(s->act));
+  return 0;
 }
 
 static int launch(Go1Sim* s, int mode, const float* actions, const int32_t* ids, int n_ids, hipStream_t st, bool timed,

@@ -244,7 +244,17 @@ class LeggedRobot(BaseTask):
         self._call_train_eval(self._randomize_rigid_body_props, torch.arange(self.num_envs, device=self.device))
         self.category_names = self.sim_meta["category_names"]
         self.curricula = self.sim_meta["curricula"]
+        # the actuator network: the reference loads resources/actuator_nets/unitree_go1.pt here (legged_robot.py:1238-1240), built
+        # into the step library; `control.actuator_net_file` (NOT a reference switch) names a retrained one, read only when the
+        # network is the torque model, as there.  One table for all environments (train and evaluation: one robot).
+        act_file = getattr(cfg.control, "actuator_net_file", None)
+        act_table = H.load_actuator_net(act_file) if act_file is not None and cfg.control.control_type == "actuator_net" else None
         self.sim = H.Go1Sim(self.sim_config, B, self.sim_device_id)
+        if act_table is not None:
+            if not callable(getattr(self.sim, "set_actuator_net", None)):
+                raise RuntimeError(f"Cfg.control.actuator_net_file = {act_file!r}: the simulator {type(self.sim).__name__} cannot load an "
+                                   f"actuator network (it only has the built-in one); set actuator_net_file = None to run with that")
+            self.sim.set_actuator_net(act_table)
         self.sim_config_eval = None
         if self.eval_cfg is not None:
             # evaluation environments: the train block with the fields the reference dispatches per group taken from

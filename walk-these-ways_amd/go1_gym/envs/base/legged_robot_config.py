@@ -83,6 +83,9 @@ _DEFAULTS = dict(
     control=dict(
         control_type='actuator_net', stiffness={'joint_a': 10.0, 'joint_b': 15.},
         damping={'joint_a': 1.0, 'joint_b': 1.5}, action_scale=0.5, hip_scale_reduction=1.0, decimation=4,
+        # (NOT a reference switch, so not declared here — the defaults must stay the reference's, tests/test_dropin_config.py:
+        #  `actuator_net_file`, read with getattr, default None: a TorchScript actuator network, the reference trainer's output,
+        #  that replaces the built-in unitree_go1.pt when control_type == 'actuator_net'; legged_robot.py create_sim)
     ),
     asset=dict(
         file="", foot_name="None", penalize_contacts_on=[], terminate_after_contacts_on=[], disable_gravity=False,

@@ -527,6 +527,90 @@ def make_eval_sim_config(S_train, S_from_eval_cfg):
 
 
 # ---------------------------------------------------------------------------------------------
+# ---- the actuator network as a run-time input (include/go1sim.h Go1ActuatorTable) --------------------------------------------
+ACT_TABLE_FLOATS = abi.GO1_ACT_TABLE_FLOATS
+_NI, _NH = abi.GO1_ACT_INPUTS, abi.GO1_ACT_HIDDEN
+# parameters of the reference trainer's build_mlp(in_dim=6, units=32, layers=2, out_dim=1, act='softsign') (scripts/actuator_net/
+# utils.py:66-72,93), in the table's field order; the activations (modules 1 and 3) carry none
+ACT_PARAMS = (("0.weight", (_NH, _NI)), ("0.bias", (_NH,)), ("2.weight", (_NH, _NH)), ("2.bias", (_NH,)),
+              ("4.weight", (1, _NH)), ("4.bias", (1,)))
+_FP16_MAX = 65504.0
+
+
+def actuator_probe_inputs(n=4096, seed=0):
+    """A fixed (n, 6) float64 probe set of actuator-network inputs (position errors in rad, joint velocities in rad/s, each with
+    its two previous values): half in the range a walking Go1 meets (errors within 0.3 rad, velocities within 10 rad/s), half out
+    to falls and resets (1.5 rad, 30 rad/s)."""
+    rng = np.random.default_rng(seed)
+    scale = np.where(np.arange(n)[:, None] < n // 2, [0.3, 0.3, 0.3, 10.0, 10.0, 10.0], [1.5, 1.5, 1.5, 30.0, 30.0, 30.0])
+    return rng.uniform(-1.0, 1.0, (n, _NI)) * scale
+
+
+def actuator_net_eval(table, x):
+    """The softsign MLP of a table (GO1_ACT_TABLE_FLOATS floats) on inputs x (n, 6), in float64: (n,) torques."""
+    t = np.asarray(table, dtype=np.float64)
+    o, parts = 0, []
+    for _, shape in ACT_PARAMS:
+        k = int(np.prod(shape))
+        parts.append(t[o:o + k].reshape(shape))
+        o += k
+    w0, b0, w1, b1, w2, b2 = parts
+    ss = lambda v: v / (1.0 + np.abs(v))             # noqa: E731
+    return (ss(ss(np.asarray(x, np.float64) @ w0.T + b0) @ w1.T + b1) @ w2.T + b2)[:, 0]
+
+
+def load_actuator_net(path):
+    """Read an actuator network saved as TorchScript (the reference trainer's `torch.jit.script(model).save(path)`,
+    scripts/actuator_net/utils.py:144-145) into the step library's table: np.float32[GO1_ACT_TABLE_FLOATS].
+
+    Only the network the kernels evaluate is accepted: Linear(6, 32), softsign, Linear(32, 32), softsign, Linear(32, 1), with
+    the parameters named as nn.Sequential names them.  The activation modules are not checked by name: the loaded module itself
+    is evaluated in float64 on actuator_probe_inputs() and must agree with the softsign network of the extracted weights (an
+    `elu` network, an extra layer or a scaling of the inputs inside the module is refused).  Every weight must be finite and
+    every |W1| within the fp16 range (the matrix-core path splits W1 into fp16 hi + lo)."""
+    path = os.fspath(path)
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"actuator network {path!r}: no such file")
+    try:
+        module = torch.jit.load(path, map_location="cpu")
+    except Exception as exc:
+        raise ValueError(f"actuator network {path!r}: not a TorchScript file ({exc})") from exc
+    params = {name: p.detach().float().clone() for name, p in module.named_parameters()}
+    want = dict(ACT_PARAMS)
+    if set(params) != set(want):
+        raise ValueError(f"actuator network {path!r}: parameters {sorted(params)}, expected {sorted(want)} "
+                         f"(Linear(6, 32), softsign, Linear(32, 32), softsign, Linear(32, 1))")
+    for name, shape in ACT_PARAMS:
+        if tuple(params[name].shape) != shape:
+            raise ValueError(f"actuator network {path!r}: {name} has shape {tuple(params[name].shape)}, expected {shape} "
+                             f"(only the 6 -> 32 -> 32 -> 1 network is supported)")
+    table = np.concatenate([params[name].reshape(-1).numpy() for name, _ in ACT_PARAMS]).astype(np.float32)
+    assert table.size == ACT_TABLE_FLOATS
+    if not np.isfinite(table).all():
+        bad = [name for name, _ in ACT_PARAMS if not torch.isfinite(params[name]).all()]
+        raise ValueError(f"actuator network {path!r}: non-finite weights in {bad}")
+    w1max = float(params["2.weight"].abs().max())
+    if w1max > _FP16_MAX:
+        raise ValueError(f"actuator network {path!r}: max |2.weight| = {w1max:g} exceeds the fp16 range ({_FP16_MAX:g}) of the "
+                         f"step kernel's hidden layer")
+    x = actuator_probe_inputs()
+    try:
+        with torch.no_grad():
+            got = module.double()(torch.from_numpy(x)).reshape(-1).numpy()
+    except Exception as exc:
+        raise ValueError(f"actuator network {path!r}: evaluating the module on (n, 6) float64 inputs failed ({exc})") from exc
+    ref = actuator_net_eval(table, x)
+    if got.shape != ref.shape:
+        raise ValueError(f"actuator network {path!r}: output of shape {got.shape} for {len(x)} input rows, expected one torque per row")
+    err = np.abs(got - ref)
+    worst = int(np.argmax(err / (1.0 + np.abs(ref))))
+    if not err[worst] <= 1e-9 * (1.0 + abs(ref[worst])):
+        raise ValueError(f"actuator network {path!r}: the module is not the softsign network of its weights (torque {got[worst]:.6g} "
+                         f"against {ref[worst]:.6g} at input {x[worst].round(3).tolist()}): only Linear(6, 32), softsign, "
+                         f"Linear(32, 32), softsign, Linear(32, 1) is supported")
+    return table
+
+
 _lib = None
 
 
@@ -566,11 +650,14 @@ def bind_library(lib):
     lib.go1sim_set_counters.argtypes = [vp, i64, i32]
     lib.go1sim_enable_timing.argtypes = [vp, ctypes.c_int]
     lib.go1sim_read_timings.argtypes = [vp, ctypes.POINTER(ctypes.c_float), i32, ctypes.POINTER(i32)]
+    lib.go1sim_set_actuator_net.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
+    lib.go1sim_get_actuator_net.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     lib.go1sim_version.restype = ctypes.c_char_p
     for fn in ("go1sim_create", "go1sim_destroy", "go1sim_set_config", "go1sim_set_eval_config", "go1sim_step", "go1sim_reset_idx",
                "go1sim_compute_torques", "go1sim_physics_substep", "go1sim_curriculum_update", "go1sim_post_physics",
                "go1sim_append_history", "go1sim_history_window_offset",
-               "go1sim_get_counters", "go1sim_set_counters", "go1sim_enable_timing", "go1sim_read_timings"):
+               "go1sim_get_counters", "go1sim_set_counters", "go1sim_enable_timing", "go1sim_read_timings",
+               "go1sim_set_actuator_net", "go1sim_get_actuator_net"):
         getattr(lib, fn).restype = ctypes.c_int
     return lib
 
@@ -579,7 +666,7 @@ EXPORTED_SYMBOLS = ["go1sim_create", "go1sim_destroy", "go1sim_set_config", "go1
                     "go1sim_compute_torques", "go1sim_physics_substep", "go1sim_curriculum_update",
                     "go1sim_post_physics", "go1sim_append_history", "go1sim_history_window_offset",
                     "go1sim_get_counters", "go1sim_set_counters", "go1sim_enable_timing",
-                    "go1sim_read_timings", "go1sim_version"]
+                    "go1sim_read_timings", "go1sim_set_actuator_net", "go1sim_get_actuator_net", "go1sim_version"]
 
 
 class Go1Sim:
@@ -647,6 +734,23 @@ class Go1Sim:
         """environments [num_train_envs, N) run under S_eval (make_eval_sim_config); num_train_envs % 16 == 0"""
         self.S_eval, self.num_train_envs = S_eval, int(num_train_envs)
         self._check(self.lib.go1sim_set_eval_config(self.handle, ctypes.byref(S_eval), int(num_train_envs)), "go1sim_set_eval_config")
+
+    def set_actuator_net(self, table=None):
+        """Install an actuator network (np.float32[GO1_ACT_TABLE_FLOATS], load_actuator_net) for every environment; None restores the
+        built-in one.  Blocking; kept across set_config / set_eval_config."""
+        if table is None:
+            self._check(self.lib.go1sim_set_actuator_net(self.handle, None), "go1sim_set_actuator_net")
+            return
+        t = np.ascontiguousarray(table, dtype=np.float32).reshape(-1)
+        if t.size != ACT_TABLE_FLOATS:
+            raise ValueError(f"actuator table of {t.size} floats, expected {ACT_TABLE_FLOATS}")
+        self._check(self.lib.go1sim_set_actuator_net(self.handle, t.ctypes.data_as(ctypes.POINTER(ctypes.c_float))), "go1sim_set_actuator_net")
+
+    def actuator_net(self):
+        """The actuator table in force: np.float32[GO1_ACT_TABLE_FLOATS]."""
+        t = np.empty(ACT_TABLE_FLOATS, dtype=np.float32)
+        self._check(self.lib.go1sim_get_actuator_net(self.handle, t.ctypes.data_as(ctypes.POINTER(ctypes.c_float))), "go1sim_get_actuator_net")
+        return t
 
     def counters(self):
         c, h = ctypes.c_int64(), ctypes.c_int32()
