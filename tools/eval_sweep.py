@@ -1,0 +1,94 @@
+"""Evaluate a trained policy over a grid of commands under the reference's domain-randomisation presets
+(go1_gym_learn/eval_metrics): for every preset one rollout of `--envs` environments, the ten scalar metrics accumulated on
+the device (include/go1eval.h), one table per preset.
+
+    python tools/eval_sweep.py --checkpoint RUN_DIR/checkpoints --presets static_medium rand_large --vx 0.5 1.0 1.5 --out RUN_DIR
+
+The checkpoint directory holds `ac_weights_last.pt` (the Runner's state dict) or the exported TorchScript pair
+`adaptation_module_latest.jit` + `body_latest.jit`.  Writes `<out>/eval/<preset>.json` and prints a Markdown table per preset.
+Run on the GPU box."""
+import argparse
+import json
+import os
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(REPO, "walk-these-ways_amd")
+for p in (os.path.join(PKG, "shims"), PKG, REPO):
+    sys.path.insert(0, p)
+import torch  # noqa: E402
+
+
+class ScriptedPolicy:
+    """the exported TorchScript pair behind the ActorCritic's inference surface"""
+
+    def __init__(self, adaptation_module, body):
+        self.adaptation_module, self.body = adaptation_module, body
+
+    def _latent(self, observation_history):
+        return self.adaptation_module(observation_history)
+
+    def _actor(self, observation_history, latent):
+        return self.body(torch.cat((observation_history, latent), dim=-1))
+
+    def act_inference(self, obs, policy_info={}):
+        h = obs["obs_history"]
+        return self._actor(h, self._latent(h))
+
+
+def load_policy(checkpoint_dir, device):
+    """ac_weights_last.pt if present (its shapes give the ActorCritic's sizes), else the TorchScript pair"""
+    weights = os.path.join(checkpoint_dir, "ac_weights_last.pt")
+    if os.path.exists(weights):
+        from go1_gym_learn.ppo_cse.actor_critic import ActorCritic
+        sd = torch.load(weights, map_location=device)
+        first, last = sd["adaptation_module.0.weight"], [k for k in sd if k.startswith("adaptation_module.") and k.endswith(".weight")][-1]
+        num_obs_history, num_priv = first.shape[1], sd[last].shape[0]
+        num_actions = sd["std"].shape[0]
+        policy = ActorCritic(0, num_priv, num_obs_history, num_actions).to(device)
+        policy.load_state_dict(sd)
+        return policy.eval()
+    adapt, body = (os.path.join(checkpoint_dir, n) for n in ("adaptation_module_latest.jit", "body_latest.jit"))
+    if os.path.exists(adapt) and os.path.exists(body):
+        return ScriptedPolicy(torch.jit.load(adapt, map_location=device), torch.jit.load(body, map_location=device))
+    raise FileNotFoundError(f"{checkpoint_dir}: neither ac_weights_last.pt nor adaptation_module_latest.jit + body_latest.jit")
+
+
+def to_json(result):
+    return dict(preset=result["preset"], num_envs=result["num_envs"], steps=result["steps"], warmup_steps=result["warmup_steps"],
+                seed=result["seed"], cells=[dict(vx=c[0], yaw=c[1], gait=list(c[2])) for c in result["cells"]],
+                fields=["count", "mean", "std", "min", "max", "nonfinite"],
+                metrics={k: v.tolist() for k, v in result["metrics"].items()},
+                group_fields=["envs", "steps", "episodes_terminated", "episodes_timed_out", "fall_rate"], groups=result["groups"].tolist())
+
+
+def main(argv=None):
+    from go1_gym_learn.eval_metrics import sweep
+    from go1_gym_learn.eval_metrics.domain_randomization import DR_SETTINGS
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--checkpoint", required=True)
+    ap.add_argument("--presets", nargs="+", default=["static_medium", "rand_large"], choices=sorted(DR_SETTINGS))
+    ap.add_argument("--vx", nargs="+", type=float, default=[0.5, 1.0, 1.5])
+    ap.add_argument("--yaw", nargs="+", type=float, default=[0.0])
+    ap.add_argument("--gaits", nargs="+", default=["trotting"], choices=sorted(sweep.GAITS))
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--steps", type=int, default=500)
+    ap.add_argument("--warmup-steps", type=int, default=25)
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--terrain", default=None, choices=["plane", "heightfield", "trimesh"])
+    ap.add_argument("--out", required=True)
+    a = ap.parse_args(argv)
+    assert torch.cuda.is_available(), "eval_sweep needs a GPU"
+    policy = load_policy(a.checkpoint, "cuda:0")
+    grid = dict(vx=a.vx, yaw=a.yaw, gait=[sweep.GAITS[g] for g in a.gaits])
+    os.makedirs(os.path.join(a.out, "eval"), exist_ok=True)
+    for preset in a.presets:
+        res = sweep.run_sweep(policy, preset, grid, num_envs=a.envs, steps=a.steps, warmup_steps=a.warmup_steps, seed=a.seed, terrain=a.terrain)
+        with open(os.path.join(a.out, "eval", preset + ".json"), "w") as f:
+            json.dump(to_json(res), f, indent=1)
+        print(f"### {preset}: {a.envs} environments, {a.steps} steps\n")
+        print(sweep.markdown_table(res) + "\n")
+
+
+if __name__ == "__main__":
+    main()

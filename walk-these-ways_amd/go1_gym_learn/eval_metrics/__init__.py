@@ -1,0 +1,3 @@
+"""Evaluation of trained policies: the reference's metric functions and domain-randomisation presets under their own names
+(`metrics.METRICS_FNS`, `domain_randomization.DR_SETTINGS`), and `sweep.run_sweep`, which measures the ten scalar metrics on
+the device (include/go1eval.h) over a grid of commands."""

@@ -1,0 +1,147 @@
+"""Host side of the evaluation-metrics C-ABI (include/go1eval.h): ctypes mirror, library loading, and `Go1Eval`, which owns
+the per-environment accumulators and the result table of one simulator instance.
+
+Replaces calling the reference's go1_gym_learn/eval_metrics/metrics.py functions (each ends in `.cpu()`) after every step:
+`accumulate()` enqueues one launch and the host reads one small table when it asks for `results()`.
+"""
+import ctypes
+import os
+
+import numpy as np
+import torch
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "csrc", "libgo1eval.so")
+
+METRIC_NAMES = ["lin_vel_rmsd", "ang_vel_rmsd", "lin_vel_x", "ang_vel_yaw", "base_height", "max_torques", "power_consumption",
+                "CoT", "froude_number", "termination"]                                        # enum Go1EvalMetric
+FIELD_NAMES = ["count", "mean", "std", "min", "max", "nonfinite"]                             # enum Go1EvalField
+GROUP_FIELD_NAMES = ["envs", "steps", "episodes_terminated", "episodes_timed_out", "fall_rate"]   # enum Go1EvalGroupField
+NUM_METRICS, NUM_FIELDS, REDUCE_THREADS = 10, 6, 256
+DEFAULT_BODY_MASS = 4.801          # LeggedRobot.default_body_mass
+
+
+class Go1EvalConfig(ctypes.Structure):
+    _fields_ = [("num_envs", ctypes.c_int32), ("num_height_points", ctypes.c_int32), ("warmup_steps", ctypes.c_int32),
+                ("num_groups", ctypes.c_int32), ("default_body_mass", ctypes.c_float)]
+
+
+_INPUTS = ["base_lin_vel", "base_ang_vel", "commands", "root_states", "measured_heights", "torques", "dof_vel", "payloads",
+           "reset_buf", "time_out_buf", "episode_length_buf"]
+_ACCUMULATORS = ["count", "sum", "sumsq", "min", "max", "nonfinite"]
+_PER_ENV = ["steps", "episodes_terminated", "episodes_timed_out"]
+
+
+class Go1EvalBuffers(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in _INPUTS + _ACCUMULATORS + _PER_ENV + ["group", "results"]]
+
+
+EXPORTED_SYMBOLS = ["go1eval_clear", "go1eval_accumulate", "go1eval_reduce", "go1eval_version"]
+
+_lib = None
+
+
+class Go1EvalLibraryMissing(RuntimeError):
+    pass
+
+
+def load_library(path=None):
+    """Load libgo1eval.so (HIP, gfx950).  Fails loudly: the metrics kernels have no CPU fallback."""
+    global _lib
+    if path is None and _lib is not None:
+        return _lib
+    p = path or LIB_PATH
+    if not os.path.exists(p):
+        raise Go1EvalLibraryMissing(
+            f"{p} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+            f"(hipcc --offload-arch=gfx950). Device-side evaluation metrics have no CPU fallback.")
+    lib = ctypes.CDLL(p)
+    cfg_p, buf_p = ctypes.POINTER(Go1EvalConfig), ctypes.POINTER(Go1EvalBuffers)
+    for fn in ("go1eval_clear", "go1eval_accumulate", "go1eval_reduce"):
+        getattr(lib, fn).argtypes = [cfg_p, buf_p, ctypes.c_void_p]
+        getattr(lib, fn).restype = ctypes.c_int
+    lib.go1eval_version.restype = ctypes.c_char_p
+    if path is None:
+        _lib = lib
+    return lib
+
+
+_ACC_DTYPES = {"count": torch.int32, "sum": torch.float64, "sumsq": torch.float64, "min": torch.float32, "max": torch.float32,
+               "nonfinite": torch.int32}          # (uint32 on the device; torch reads the same bits as int32)
+
+
+class Go1Eval:
+    """Metrics of one simulator instance.  S: its Go1SimConfig, buffers: its SimBuffers (device tensors)."""
+
+    def __init__(self, S, buffers, lib=None):
+        self.lib = lib if lib is not None else load_library()
+        self.buffers = buffers
+        self.device = buffers.device
+        N = self.num_envs = int(S.num_envs)
+        c = self.cfg = Go1EvalConfig()
+        c.num_envs, c.default_body_mass = N, DEFAULT_BODY_MASS
+        self.measure_heights = bool(S.measure_heights)
+        c.num_height_points = int(buffers.measured_heights.shape[0]) if self.measure_heights else 0
+        self.acc = {n: torch.zeros(NUM_METRICS, N, dtype=dt, device=self.device) for n, dt in _ACC_DTYPES.items()}
+        self.per_env = {n: torch.zeros(N, dtype=torch.int32, device=self.device) for n in _PER_ENV}
+        self.group = torch.full((N,), -1, dtype=torch.int32, device=self.device)
+        self.table = None
+        self.armed = False
+        self.buf = Go1EvalBuffers()
+        self._refresh()
+
+    def _refresh(self):
+        b, B = self.buf, self.buffers
+        for n in _INPUTS:
+            setattr(b, n, getattr(B, n).data_ptr())
+        if not self.measure_heights:
+            b.measured_heights = None
+        for n, t in list(self.acc.items()) + list(self.per_env.items()):
+            setattr(b, n, t.data_ptr())
+        b.group = self.group.data_ptr()
+        b.results = self.table.data_ptr() if self.table is not None else None
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise RuntimeError(f"{what} failed: {rc}")
+
+    def arm(self, groups, warmup_steps=0):
+        """start a measurement: `groups` = int group id per environment (-1: not evaluated); empties the accumulators"""
+        g = torch.as_tensor(groups).to(torch.int32).reshape(-1)
+        assert g.numel() == self.num_envs, (g.numel(), self.num_envs)
+        G = int(g.max()) + 1                                   # (on the host, before the step loop)
+        assert G >= 1, "no environment carries a group id >= 0"
+        self.group.copy_(g)
+        self.cfg.num_groups, self.cfg.warmup_steps = G, int(warmup_steps)
+        self.table = torch.zeros(G, NUM_METRICS + 1, NUM_FIELDS, dtype=torch.float64, device=self.device)
+        self._refresh()
+        self._check(self.lib.go1eval_clear(ctypes.byref(self.cfg), ctypes.byref(self.buf), self._stream()), "go1eval_clear")
+        self.armed = True
+
+    def accumulate(self):
+        """after a step: fold it into the accumulators (one launch, no sync)"""
+        self._check(self.lib.go1eval_accumulate(ctypes.byref(self.cfg), ctypes.byref(self.buf), self._stream()), "go1eval_accumulate")
+
+    def disarm(self):
+        """stop folding steps (the accumulators keep what they hold for `results()`)"""
+        self.armed = False
+
+    def reduce(self):
+        """the result table [G][NUM_METRICS + 1][NUM_FIELDS] as a device tensor (one launch, no sync)"""
+        assert self.table is not None, "arm() first"
+        self._check(self.lib.go1eval_reduce(ctypes.byref(self.cfg), ctypes.byref(self.buf), self._stream()), "go1eval_reduce")
+        return self.table
+
+    def results(self):
+        """{metric name: (G, 6) array with the columns FIELD_NAMES, "groups": (G, 5) array with the columns GROUP_FIELD_NAMES}:
+        one launch and one device-to-host copy"""
+        return table_to_dict(self.reduce().cpu().numpy())
+
+
+def table_to_dict(table):
+    out = {name: table[:, m, :].copy() for m, name in enumerate(METRIC_NAMES)}
+    out["groups"] = table[:, NUM_METRICS, :len(GROUP_FIELD_NAMES)].copy()
+    return out
