@@ -50,6 +50,67 @@
  *   empty group; the definition of tools/play_eval.py), 0.
  *   Fixed combination order: thread t of GO1EVAL_REDUCE_THREADS combines environments t, t + T, t + 2T, ... in ascending order,
  *   then a binary tree over the threads (stride T/2, T/4, ... 1: thread t takes thread t + stride).  Same inputs, same bits.
+ *
+ * ---- the behaviour table (second kernel family; index = Go1BehaviourMetric) --------------------------------------------------
+ * The ten metrics above say how well a policy tracks a velocity.  The behaviour table says whether it does what the other
+ * commands ask (body height, step frequency, gait, duty factor, foot swing, pitch and roll, stance width and length), from the
+ * simulator's SoA buffers after a step, with the same accumulators, the same folding rule and the same reduction.
+ *
+ * A foot f (0..3) is body 4 + 4 f of contact_forces ([17 * 3][N]) and rows 3 f .. 3 f + 2 of foot_positions / foot_velocities.
+ * It is IN CONTACT when its F_z > 1.0 (the reference's threshold).  cmd[k] = commands[k][e].
+ *
+ * Seven per-step metrics (fp32; a sum over feet or joints adds its fp32 terms in an fp64 carry, feet / joints in ascending
+ * order, and rounds to fp32 once, as base_height and power_consumption do above):
+ *   contact_match      0.25 * number of feet with [F_z > 1.0] == [desired_contact_states[f] > 0.5]   (tools/play_eval.py's figure)
+ *   body_height_err    height - (cmd[3] + base_height_target), signed; height is the metric base_height above (root z minus the
+ *                      mean of measured_heights; root z when measured_heights is NULL)
+ *   orientation_err    sqrt(dx^2 + dy^2), d = R(q)^T (0, 0, -1) - R(qc)^T (0, 0, -1): q the base quaternion root_states[3..6]
+ *                      (xyzw), qc = roll(-cmd[11]) about x  *  pitch(-cmd[10]) about y, the composition of the reference's
+ *                      _reward_orientation_control, i.e. qc = (sr cp, cr sp, sr sp, cr cp) with sr, cr = sin, cos(-cmd[11] / 2) and
+ *                      sp, cp = sin, cos(-cmd[10] / 2).  R(q)^T v = v + w t + u x t with u = -q.xyz, t = 2 (u x v).  Computed from
+ *                      the quaternion and the fixed vector (0, 0, -1), not from projected_gravity: gravity randomisation does not
+ *                      show up as an attitude error.
+ *   feet_clearance     sum over the feet of (cmd[9] * ph + 0.02 - z_f)^2 * (1 - desired_contact_states[f]),
+ *                      ph = 1 - |1 - 2 clip(2 foot_indices[f] - 1, 0, 1)|  (the reference's _reward_feet_clearance_cmd_linear).
+ *                      z_f is the foot's WORLD z as there: meaningful on flat ground only.
+ *   raibert_heuristic  sum over the feet of (xs + xo - bx)^2 + (ys + yo - by)^2  (the reference's _reward_raibert_heuristic):
+ *                      (bx, by) = the foot's position minus the base position, rotated by the inverse yaw of the base, the yaw
+ *                      quaternion being (0, 0, -q.z, q.w) / max(sqrt(q.z^2 + q.w^2), 1e-9);
+ *                      width = cmd[12] if num_commands >= 13 else 0.3, length = cmd[13] if num_commands >= 14 else 0.45;
+ *                      xs = +length / 2 (feet 0, 1), -length / 2 (feet 2, 3);  ys = +width / 2 (feet 0, 2), -width / 2 (feet 1, 3);
+ *                      ph = |1 - 2 foot_indices[f]| - 0.5;  xo = ph * cmd[0] * (0.5 / cmd[4]);
+ *                      yo = ph * (cmd[2] * length / 2) * (0.5 / cmd[4]), negated for feet 2, 3.  cmd[4] = 0 gives a non-finite value.
+ *   feet_slip          sum over the feet IN CONTACT of v_x^2 + v_y^2 (foot_velocities).  The reference's _reward_feet_slip without
+ *                      its previous-step filter: it does not depend on last_contacts, which only an active reward term maintains.
+ *   action_rate        sum over the 12 joints of (last_actions[j] - last_last_actions[j])^2; after a step last_actions holds this
+ *                      step's action and last_last_actions the one before.
+ *
+ * Three per-stride metrics, folded at a TOUCHDOWN of a foot, not every step.  Per foot the kernel carries prev_contact (0, 1, or
+ * 2 = unknown), stride_steps (-1 = no touchdown seen yet), stance_steps and swing_peak.  A touchdown of foot f is: in contact now
+ * and prev_contact[f] == 0.  At a touchdown with L = stride_steps[f] >= 0 a stride of L steps has just ended, and with the
+ * commands of the touchdown step
+ *   step_frequency_err = 1 / (L * dt) - cmd[4]
+ *   duty_factor_err    = stance_steps[f] / L - cmd[8]
+ *   swing_height_err   = (swing_peak[f] - 0.02) - cmd[9]
+ * are folded (L and stance_steps converted to fp32; L >= 2 by construction).  After folding, or after skipping the fold because
+ * stride_steps[f] < 0, stride_steps[f] = 0, stance_steps[f] = 0, swing_peak[f] = -inf.  Then, touchdown or not:
+ *   stride_steps[f] += 1 if it is >= 0;  stance_steps[f] += 1 if the foot is in contact;
+ *   swing_peak[f] = max(swing_peak[f], z_f);  prev_contact[f] = contact.
+ * So swing_peak is the largest world z of the foot from the touchdown step to the step before the next touchdown, and 0.02 is
+ * the reference's foot radius.  There is NO DEBOUNCE: a chattering contact ends strides of two or three steps and shows up as a
+ * high step frequency, which is what it is.
+ *
+ * go1eval_behaviour_accumulate, per environment e (one thread each; every accumulator and every state word has one writer), in
+ * this order:
+ *   1. reset_buf[e] != 0, or episode_length_buf[e] <= warmup_steps: nothing is folded; all four feet go to prev_contact = 2,
+ *      stride_steps = -1 (stance_steps and swing_peak are left: the next touchdown resets them before they are read).  A stride
+ *      never spans a reset or the warm-up.
+ *   2. otherwise the seven per-step metrics are folded, then feet 0, 1, 2, 3 are advanced in that order by the rules above: two
+ *      touchdowns in one step fold in a fixed order.
+ *   Folding is the rule of go1eval_accumulate: a non-finite value is counted in nonfinite and enters nothing else.
+ * go1eval_behaviour_clear: accumulators as go1eval_clear; prev_contact = 2, stride_steps = -1, stance_steps = 0, swing_peak = -inf.
+ * go1eval_behaviour_reduce: the metric rows of go1eval_reduce, the same fixed combination order (the same device function), into
+ * results[num_groups][GO1EVAL_NUM_BEHAVIOUR][GO1EVAL_NUM_FIELDS].  There is no group row; the first table has it.
  */
 #ifndef GO1EVAL_H_INCLUDED
 #define GO1EVAL_H_INCLUDED
@@ -120,6 +181,68 @@ int go1eval_accumulate(const Go1EvalConfig* cfg, const Go1EvalBuffers* buf, void
 
 /* at the end: the result table from the accumulators (which it leaves as they are).  One launch. */
 int go1eval_reduce(const Go1EvalConfig* cfg, const Go1EvalBuffers* buf, void* stream);
+
+/* ---- the behaviour table ---------------------------------------------------------------------------------------------------- */
+#define GO1EVAL_NUM_BEHAVIOUR 10
+#define GO1EVAL_CONTACT_FORCE 1.0    /* N: a foot is in contact when its F_z exceeds this (the reference's threshold) */
+#define GO1EVAL_FOOT_RADIUS 0.02     /* m: the reference's offset between a foot's origin and its sole */
+
+enum Go1BehaviourMetric {
+  GO1EVAL_CONTACT_MATCH = 0, GO1EVAL_BODY_HEIGHT_ERR = 1, GO1EVAL_ORIENTATION_ERR = 2, GO1EVAL_FEET_CLEARANCE = 3,
+  GO1EVAL_RAIBERT_HEURISTIC = 4, GO1EVAL_FEET_SLIP = 5, GO1EVAL_ACTION_RATE = 6, GO1EVAL_STEP_FREQUENCY_ERR = 7,
+  GO1EVAL_DUTY_FACTOR_ERR = 8, GO1EVAL_SWING_HEIGHT_ERR = 9
+};
+
+typedef struct Go1BehaviourConfig {
+  int32_t num_envs;            /* N of the simulator's SoA buffers */
+  int32_t num_commands;        /* the configuration's command count: below 13 / 14 the stance width / length are the defaults */
+  int32_t num_height_points;   /* rows of measured_heights (ignored when it is NULL) */
+  int32_t warmup_steps;        /* steps with episode_length_buf <= warmup_steps fold nothing and break every stride */
+  int32_t num_groups;          /* G of the result table */
+  float dt;                    /* s, the policy step (simulation step x decimation) */
+  float base_height_target;    /* m, the reference's rewards.base_height_target */
+} Go1BehaviourConfig;
+
+typedef struct Go1BehaviourBuffers {
+  /* read by go1eval_behaviour_accumulate */
+  const float* commands;                /* [>= max(12, min(num_commands, 14))][N] */
+  const float* root_states;             /* [13][N]; rows 0..6 are read */
+  const float* measured_heights;        /* [num_height_points][N] or NULL (the ground is 0) */
+  const float* contact_forces;          /* [17 * 3][N]; the feet are bodies 4, 8, 12, 16 */
+  const float* foot_positions;          /* [4 * 3][N], world frame */
+  const float* foot_velocities;         /* [4 * 3][N], world frame */
+  const float* desired_contact_states;  /* [4][N] */
+  const float* foot_indices;            /* [4][N] */
+  const float* last_actions;            /* [12][N]: this step's action */
+  const float* last_last_actions;       /* [12][N]: the previous step's */
+  const uint8_t* reset_buf;             /* [N] */
+  const int32_t* episode_length_buf;    /* [N] */
+  /* accumulators, [GO1EVAL_NUM_BEHAVIOUR][N] */
+  uint32_t* count;
+  double* sum;
+  double* sumsq;
+  float* min;
+  float* max;
+  uint32_t* nonfinite;
+  /* per-foot stride state, [4][N] */
+  uint8_t* prev_contact;
+  int32_t* stride_steps;
+  int32_t* stance_steps;
+  float* swing_peak;
+  /* go1eval_behaviour_reduce */
+  const int32_t* group;                 /* [N] */
+  double* results;                      /* [num_groups][GO1EVAL_NUM_BEHAVIOUR][GO1EVAL_NUM_FIELDS] */
+} Go1BehaviourBuffers;
+
+/* empty accumulators and unknown stride state.  One launch. */
+int go1eval_behaviour_clear(const Go1BehaviourConfig* cfg, const Go1BehaviourBuffers* buf, void* stream);
+
+/* after a simulator step: fold the step into the accumulators and advance the stride state.  One launch, one thread per environment.
+ * num_commands < 12 (the commanded pitch and roll are rows 10, 11) or dt <= 0 is refused before the launch. */
+int go1eval_behaviour_accumulate(const Go1BehaviourConfig* cfg, const Go1BehaviourBuffers* buf, void* stream);
+
+/* at the end: the result table from the accumulators (which it leaves as they are).  One launch. */
+int go1eval_behaviour_reduce(const Go1BehaviourConfig* cfg, const Go1BehaviourBuffers* buf, void* stream);
 
 /* "go1eval <version> (gfx950) go1-src:<16 hex digits of the source hash>" */
 const char* go1eval_version(void);

@@ -6,6 +6,12 @@ the device (include/go1eval.h), one table per preset.
 
 The checkpoint directory holds `ac_weights_last.pt` (the Runner's state dict) or the exported TorchScript pair
 `adaptation_module_latest.jit` + `body_latest.jit`.  Writes `<out>/eval/<preset>.json` and prints a Markdown table per preset.
+
+    python tools/eval_sweep.py --checkpoint RUN_DIR/checkpoints --out RUN_DIR --behaviour --axis frequency 2 3 4 --axis footswing_height 0.05 0.15
+
+With `--behaviour` the sweep runs over the product of the `--axis NAME V1 V2 ...` command values instead (names:
+go1_gym_learn.eval_metrics.behaviour.COMMAND_INDEX), both tables are accumulated on the device, `<out>/eval/<preset>_behaviour.json`
+is written and the commanded-versus-realised table is printed.
 Run on the GPU box."""
 import argparse
 import json
@@ -62,7 +68,7 @@ def to_json(result):
                 group_fields=["envs", "steps", "episodes_terminated", "episodes_timed_out", "fall_rate"], groups=result["groups"].tolist())
 
 
-def main(argv=None):
+def parse_args(argv=None):
     from go1_gym_learn.eval_metrics import sweep
     from go1_gym_learn.eval_metrics.domain_randomization import DR_SETTINGS
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -76,12 +82,43 @@ def main(argv=None):
     ap.add_argument("--warmup-steps", type=int, default=25)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--terrain", default=None, choices=["plane", "heightfield", "trimesh"])
+    ap.add_argument("--behaviour", action="store_true", help="measure gait and behaviour tracking over the --axis product instead of the velocity grid")
+    ap.add_argument("--axis", nargs="+", action="append", metavar=("NAME", "VALUE"), help="a behaviour command and its values; repeatable")
     ap.add_argument("--out", required=True)
-    a = ap.parse_args(argv)
+    return ap.parse_args(argv)
+
+
+def behaviour_axes(a):
+    """{command name: [values]} of the --axis options, in the order given"""
+    from go1_gym_learn.eval_metrics.behaviour import COMMAND_INDEX
+    if not a.axis:
+        raise SystemExit("--behaviour needs at least one --axis NAME V1 V2 ...")
+    axes = {}
+    for name, *values in a.axis:
+        if name not in COMMAND_INDEX or not values:
+            raise SystemExit(f"--axis {name}: a name of {sorted(COMMAND_INDEX)} followed by at least one value")
+        axes[name] = [float(v) for v in values]
+    return axes
+
+
+def main(argv=None):
+    from go1_gym_learn.eval_metrics import sweep
+    a = parse_args(argv)
     assert torch.cuda.is_available(), "eval_sweep needs a GPU"
     policy = load_policy(a.checkpoint, "cuda:0")
     grid = dict(vx=a.vx, yaw=a.yaw, gait=[sweep.GAITS[g] for g in a.gaits])
     os.makedirs(os.path.join(a.out, "eval"), exist_ok=True)
+    if a.behaviour:
+        from go1_gym_learn.eval_metrics import behaviour
+        axes = behaviour_axes(a)
+        for preset in a.presets:
+            res = behaviour.run_behaviour_sweep(policy, preset, axes, num_envs=a.envs, steps=a.steps, warmup_steps=a.warmup_steps, seed=a.seed,
+                                                terrain=a.terrain)
+            with open(os.path.join(a.out, "eval", preset + "_behaviour.json"), "w") as f:
+                json.dump(behaviour.behaviour_to_json(res), f, indent=1)
+            print(f"### {preset}: {a.envs} environments, {a.steps} steps, behaviour\n")
+            print(behaviour.behaviour_markdown_table(res) + "\n")
+        return
     for preset in a.presets:
         res = sweep.run_sweep(policy, preset, grid, num_envs=a.envs, steps=a.steps, warmup_steps=a.warmup_steps, seed=a.seed, terrain=a.terrain)
         with open(os.path.join(a.out, "eval", preset + ".json"), "w") as f:

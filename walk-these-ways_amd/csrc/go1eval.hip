@@ -6,6 +6,9 @@
 // eval_reduce_kernel: one workgroup per (group, row of the result table).  Thread t combines environments t, t + T, ... in
 // ascending order in fp64, then a binary tree in LDS with a fixed shape; thread 0 writes the row with vector stores.
 // tests/eval_ref.py restates both in fp64 numpy from the header's text.
+// behaviour_accumulate_kernel / behaviour_reduce_kernel: the second table (gait and behaviour tracking), the same shapes: one
+// thread per environment that also carries the per-foot stride state ([4][N], one writer per word), and the metric-row reduction
+// shared with eval_reduce_kernel (reduce_metric_row).  tests/behaviour_ref.py is their fp64 model.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -22,7 +25,13 @@ struct EvalArgs {
   Go1EvalBuffers b;
 };
 
-__device__ __forceinline__ void fold(const Go1EvalBuffers& b, int m, int N, int e, float v) {
+struct BehaviourArgs {
+  Go1BehaviourConfig c;
+  Go1BehaviourBuffers b;
+};
+
+template <class Buffers>
+__device__ __forceinline__ void fold(const Buffers& b, int m, int N, int e, float v) {
   const size_t i = (size_t)m * N + e;
   if (!isfinite(v)) { b.nonfinite[i] += 1u; return; }
   b.count[i] += 1u;
@@ -31,6 +40,49 @@ __device__ __forceinline__ void fold(const Go1EvalBuffers& b, int m, int N, int 
   b.min[i] = fminf(b.min[i], v);
   b.max[i] = fmaxf(b.max[i], v);
 }
+
+// one metric row of a result table, by one workgroup of RT threads: thread t combines the group's environments t, t + RT, ... in
+// ascending order, then the binary tree in LDS; thread 0 writes the six fields.  a0 count, a1 nonfinite, a2 sum, a3 sumsq, a4 min, a5 max
+template <class Buffers>
+__device__ __forceinline__ void reduce_metric_row(const Buffers& b, int g, int m, int N, double (*lds)[RT], double* out) {
+  const int t = (int)threadIdx.x;
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = (double)INFINITY, a5 = -(double)INFINITY;
+  for (int e = t; e < N; e += RT) {
+    if (b.group[e] != g) continue;
+    const size_t i = (size_t)m * N + e;
+    a0 += (double)b.count[i]; a1 += (double)b.nonfinite[i]; a2 += b.sum[i]; a3 += b.sumsq[i];
+    if (b.count[i] > 0u) { a4 = fmin(a4, (double)b.min[i]); a5 = fmax(a5, (double)b.max[i]); }
+  }
+  lds[0][t] = a0; lds[1][t] = a1; lds[2][t] = a2; lds[3][t] = a3; lds[4][t] = a4; lds[5][t] = a5;
+  __syncthreads();
+  for (int s = RT / 2; s > 0; s >>= 1) {
+    if (t < s) {
+      for (int f = 0; f < 4; f++) lds[f][t] += lds[f][t + s];
+      lds[4][t] = fmin(lds[4][t], lds[4][t + s]); lds[5][t] = fmax(lds[5][t], lds[5][t + s]);
+    }
+    __syncthreads();
+  }
+  if (t != 0) return;
+  const double nan = (double)NAN;
+  const double n = lds[0][0];
+  const double mean = n > 0.0 ? lds[2][0] / n : nan;
+  const double var = n > 0.0 ? lds[3][0] / n - mean * mean : nan;
+  out[GO1EVAL_F_COUNT] = n; out[GO1EVAL_F_MEAN] = mean; out[GO1EVAL_F_STD] = n > 0.0 ? sqrt(fmax(var, 0.0)) : nan;
+  out[GO1EVAL_F_MIN] = n > 0.0 ? lds[4][0] : nan; out[GO1EVAL_F_MAX] = n > 0.0 ? lds[5][0] : nan; out[GO1EVAL_F_NONFINITE] = lds[1][0];
+}
+
+// ---- the quaternion algebra the behaviour metrics need (xyzw), restated here: this library shares no source with the simulator
+struct V3 { float x, y, z; };
+__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+// R(q) v = v + w t + u x t, u = q.xyz, t = 2 (u x v)
+__device__ __forceinline__ V3 quat_rotate(float x, float y, float z, float w, V3 v) {
+  const V3 u = {x, y, z};
+  const V3 c = cross(u, v);
+  const V3 t = {2.0f * c.x, 2.0f * c.y, 2.0f * c.z};
+  const V3 d = cross(u, t);
+  return {v.x + w * t.x + d.x, v.y + w * t.y + d.y, v.z + w * t.z + d.z};
+}
+__device__ __forceinline__ V3 quat_rotate_inverse(float x, float y, float z, float w, V3 v) { return quat_rotate(-x, -y, -z, w, v); }
 
 }  // namespace
 
@@ -98,44 +150,149 @@ extern "C" __global__ void __launch_bounds__(RT) eval_reduce_kernel(const EvalAr
   const int N = A.c.num_envs;
   const int t = (int)threadIdx.x;
   const int g = (int)blockIdx.x / (NM + 1), m = (int)blockIdx.x % (NM + 1);
-  const bool group_row = m == NM;
   const Go1EvalBuffers& b = A.b;
-  // metric row: a0 count, a1 nonfinite, a2 sum, a3 sumsq, a4 min, a5 max.  group row: a0 envs, a1 steps, a2 terminated, a3 timed out, a4 fallen envs
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = group_row ? 0.0 : (double)INFINITY, a5 = group_row ? 0.0 : -(double)INFINITY;
+  double* out = b.results + ((size_t)g * (NM + 1) + m) * NF;
+  if (m != NM) { reduce_metric_row(b, g, m, N, lds, out); return; }
+  // the group's own row: a0 envs, a1 steps, a2 terminated, a3 timed out, a4 fallen envs
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = 0.0;
   for (int e = t; e < N; e += RT) {
     if (b.group[e] != g) continue;
-    if (group_row) {
-      a0 += 1.0; a1 += (double)b.steps[e]; a2 += (double)b.episodes_terminated[e]; a3 += (double)b.episodes_timed_out[e];
-      a4 += b.episodes_terminated[e] > 0u ? 1.0 : 0.0;
-    } else {
-      const size_t i = (size_t)m * N + e;
-      a0 += (double)b.count[i]; a1 += (double)b.nonfinite[i]; a2 += b.sum[i]; a3 += b.sumsq[i];
-      if (b.count[i] > 0u) { a4 = fmin(a4, (double)b.min[i]); a5 = fmax(a5, (double)b.max[i]); }
-    }
+    a0 += 1.0; a1 += (double)b.steps[e]; a2 += (double)b.episodes_terminated[e]; a3 += (double)b.episodes_timed_out[e];
+    a4 += b.episodes_terminated[e] > 0u ? 1.0 : 0.0;
   }
-  lds[0][t] = a0; lds[1][t] = a1; lds[2][t] = a2; lds[3][t] = a3; lds[4][t] = a4; lds[5][t] = a5;
+  lds[0][t] = a0; lds[1][t] = a1; lds[2][t] = a2; lds[3][t] = a3; lds[4][t] = a4;
   __syncthreads();
   for (int s = RT / 2; s > 0; s >>= 1) {
     if (t < s) {
-      for (int f = 0; f < 4; f++) lds[f][t] += lds[f][t + s];
-      if (group_row) { lds[4][t] += lds[4][t + s]; }
-      else { lds[4][t] = fmin(lds[4][t], lds[4][t + s]); lds[5][t] = fmax(lds[5][t], lds[5][t + s]); }
+      for (int f = 0; f < 5; f++) lds[f][t] += lds[f][t + s];
     }
     __syncthreads();
   }
   if (t != 0) return;
-  double* out = b.results + ((size_t)g * (NM + 1) + m) * NF;
-  const double nan = (double)NAN;
-  if (group_row) {
-    out[GO1EVAL_G_ENVS] = lds[0][0]; out[GO1EVAL_G_STEPS] = lds[1][0]; out[GO1EVAL_G_TERMINATED] = lds[2][0];
-    out[GO1EVAL_G_TIMED_OUT] = lds[3][0]; out[GO1EVAL_G_FALL_RATE] = lds[0][0] > 0.0 ? lds[4][0] / lds[0][0] : nan; out[5] = 0.0;
-  } else {
-    const double n = lds[0][0];
-    const double mean = n > 0.0 ? lds[2][0] / n : nan;
-    const double var = n > 0.0 ? lds[3][0] / n - mean * mean : nan;
-    out[GO1EVAL_F_COUNT] = n; out[GO1EVAL_F_MEAN] = mean; out[GO1EVAL_F_STD] = n > 0.0 ? sqrt(fmax(var, 0.0)) : nan;
-    out[GO1EVAL_F_MIN] = n > 0.0 ? lds[4][0] : nan; out[GO1EVAL_F_MAX] = n > 0.0 ? lds[5][0] : nan; out[GO1EVAL_F_NONFINITE] = lds[1][0];
+  out[GO1EVAL_G_ENVS] = lds[0][0]; out[GO1EVAL_G_STEPS] = lds[1][0]; out[GO1EVAL_G_TERMINATED] = lds[2][0];
+  out[GO1EVAL_G_TIMED_OUT] = lds[3][0]; out[GO1EVAL_G_FALL_RATE] = lds[0][0] > 0.0 ? lds[4][0] / lds[0][0] : (double)NAN; out[5] = 0.0;
+}
+
+// ---- the behaviour table --------------------------------------------------------------------------------------------------------
+constexpr int NB = GO1EVAL_NUM_BEHAVIOUR;
+
+extern "C" __global__ void __launch_bounds__(ACC_THREADS) behaviour_clear_kernel(const BehaviourArgs A) {
+  const int N = A.c.num_envs;
+  const int e = (int)(blockIdx.x * ACC_THREADS + threadIdx.x);
+  if (e >= N) return;
+  const Go1BehaviourBuffers& b = A.b;
+  for (int m = 0; m < NB; m++) {
+    const size_t i = (size_t)m * N + e;
+    b.count[i] = 0u; b.nonfinite[i] = 0u; b.sum[i] = 0.0; b.sumsq[i] = 0.0; b.min[i] = INFINITY; b.max[i] = -INFINITY;
   }
+  for (int f = 0; f < 4; f++) {
+    const size_t i = (size_t)f * N + e;
+    b.prev_contact[i] = 2; b.stride_steps[i] = -1; b.stance_steps[i] = 0; b.swing_peak[i] = -INFINITY;
+  }
+}
+
+extern "C" __global__ void __launch_bounds__(ACC_THREADS) behaviour_accumulate_kernel(const BehaviourArgs A) {
+  const int N = A.c.num_envs;
+  const int e = (int)(blockIdx.x * ACC_THREADS + threadIdx.x);
+  if (e >= N) return;
+  const Go1BehaviourBuffers& b = A.b;
+  if (b.reset_buf[e] || b.episode_length_buf[e] <= A.c.warmup_steps) {      // a stride never spans a reset or the warm-up
+    for (int f = 0; f < 4; f++) { b.prev_contact[(size_t)f * N + e] = 2; b.stride_steps[(size_t)f * N + e] = -1; }
+    return;
+  }
+  const auto row = [N, e](const float* p, int k) { return p[(size_t)k * N + e]; };
+  const float cmd_vx = row(b.commands, 0), cmd_yaw = row(b.commands, 2), cmd_height = row(b.commands, 3), cmd_freq = row(b.commands, 4);
+  const float cmd_duty = row(b.commands, 8), cmd_swing = row(b.commands, 9), cmd_pitch = row(b.commands, 10), cmd_roll = row(b.commands, 11);
+  const float width = A.c.num_commands >= 13 ? row(b.commands, 12) : 0.3f;
+  const float length = A.c.num_commands >= 14 ? row(b.commands, 13) : 0.45f;
+  const V3 base = {row(b.root_states, 0), row(b.root_states, 1), row(b.root_states, 2)};
+  const float qx = row(b.root_states, 3), qy = row(b.root_states, 4), qz = row(b.root_states, 5), qw = row(b.root_states, 6);
+
+  bool contact[4];
+  float foot_z[4];
+  int matches = 0;
+  double clearance = 0.0, raibert = 0.0, slip = 0.0;          // (fp64 carry over fp32 terms, one rounding: see the header)
+  const float yaw_norm = fmaxf(sqrtf(qz * qz + qw * qw), 1e-9f);
+  const float yaw_z = -qz / yaw_norm, yaw_w = qw / yaw_norm;
+  const float half_period = 0.5f / cmd_freq, cmd_vy = cmd_yaw * length / 2;
+  for (int f = 0; f < 4; f++) {
+    contact[f] = row(b.contact_forces, (4 + 4 * f) * 3 + 2) > (float)GO1EVAL_CONTACT_FORCE;
+    const float desired = row(b.desired_contact_states, f), index = row(b.foot_indices, f);
+    matches += contact[f] == (desired > 0.5f) ? 1 : 0;
+    const V3 pos = {row(b.foot_positions, 3 * f), row(b.foot_positions, 3 * f + 1), row(b.foot_positions, 3 * f + 2)};
+    foot_z[f] = pos.z;
+
+    const float swing_phase = 1.0f - fabsf(1.0f - fminf(fmaxf(index * 2.0f - 1.0f, 0.0f), 1.0f) * 2.0f);
+    const float miss = cmd_swing * swing_phase + (float)GO1EVAL_FOOT_RADIUS - pos.z;
+    clearance += (double)(miss * miss * (1.0f - desired));
+
+    const V3 rel = quat_rotate(0.0f, 0.0f, yaw_z, yaw_w, V3{pos.x - base.x, pos.y - base.y, pos.z - base.z});
+    const float xs = (f < 2 ? 1.0f : -1.0f) * length / 2, ys = (f % 2 == 0 ? 1.0f : -1.0f) * width / 2;
+    const float phase = fabsf(1.0f - index * 2.0f) * 1.0f - 0.5f;
+    const float xo = phase * cmd_vx * half_period;
+    float yo = phase * cmd_vy * half_period;
+    if (f >= 2) yo = -yo;
+    const float ex = fabsf((xs + xo) - rel.x), ey = fabsf((ys + yo) - rel.y);
+    raibert += (double)(ex * ex);
+    raibert += (double)(ey * ey);
+
+    const float vx = row(b.foot_velocities, 3 * f), vy = row(b.foot_velocities, 3 * f + 1);
+    if (contact[f]) slip += (double)(vx * vx + vy * vy);
+  }
+  fold(b, GO1EVAL_CONTACT_MATCH, N, e, 0.25f * (float)matches);
+
+  float height = base.z;
+  if (b.measured_heights) {
+    double s = 0.0;
+    for (int p = 0; p < A.c.num_height_points; p++) s += (double)(base.z - b.measured_heights[(size_t)p * N + e]);
+    height = (float)s / (float)A.c.num_height_points;
+  }
+  fold(b, GO1EVAL_BODY_HEIGHT_ERR, N, e, height - (cmd_height + A.c.base_height_target));
+
+  float sr, cr, sp, cp;
+  sincosf(-cmd_roll * 0.5f, &sr, &cr);
+  sincosf(-cmd_pitch * 0.5f, &sp, &cp);
+  const V3 down = {0.0f, 0.0f, -1.0f};
+  const V3 is = quat_rotate_inverse(qx, qy, qz, qw, down);
+  const V3 want = quat_rotate_inverse(sr * cp, cr * sp, sr * sp, cr * cp, down);
+  const float dx = is.x - want.x, dy = is.y - want.y;
+  fold(b, GO1EVAL_ORIENTATION_ERR, N, e, sqrtf(dx * dx + dy * dy));
+
+  fold(b, GO1EVAL_FEET_CLEARANCE, N, e, (float)clearance);
+  fold(b, GO1EVAL_RAIBERT_HEURISTIC, N, e, (float)raibert);
+  fold(b, GO1EVAL_FEET_SLIP, N, e, (float)slip);
+
+  double rate = 0.0;
+  for (int j = 0; j < 12; j++) {
+    const float d = row(b.last_actions, j) - row(b.last_last_actions, j);
+    rate += (double)(d * d);
+  }
+  fold(b, GO1EVAL_ACTION_RATE, N, e, (float)rate);
+
+  for (int f = 0; f < 4; f++) {
+    const size_t i = (size_t)f * N + e;
+    int stride = b.stride_steps[i], stance = b.stance_steps[i];
+    float peak = b.swing_peak[i];
+    if (contact[f] && b.prev_contact[i] == 0) {                 // touchdown
+      if (stride >= 0) {
+        const float L = (float)stride;
+        fold(b, GO1EVAL_STEP_FREQUENCY_ERR, N, e, 1.0f / (L * A.c.dt) - cmd_freq);
+        fold(b, GO1EVAL_DUTY_FACTOR_ERR, N, e, (float)stance / L - cmd_duty);
+        fold(b, GO1EVAL_SWING_HEIGHT_ERR, N, e, (peak - (float)GO1EVAL_FOOT_RADIUS) - cmd_swing);
+      }
+      stride = 0; stance = 0; peak = -INFINITY;
+    }
+    if (stride >= 0) stride += 1;
+    if (contact[f]) stance += 1;
+    b.stride_steps[i] = stride; b.stance_steps[i] = stance; b.swing_peak[i] = fmaxf(peak, foot_z[f]);
+    b.prev_contact[i] = contact[f] ? 1 : 0;
+  }
+}
+
+extern "C" __global__ void __launch_bounds__(RT) behaviour_reduce_kernel(const BehaviourArgs A) {
+  __shared__ double lds[NF][RT];
+  const int g = (int)blockIdx.x / NB, m = (int)blockIdx.x % NB;
+  reduce_metric_row(A.b, g, m, A.c.num_envs, lds, A.b.results + ((size_t)g * NB + m) * NF);
 }
 
 namespace {
@@ -171,6 +328,43 @@ extern "C" int go1eval_reduce(const Go1EvalConfig* cfg, const Go1EvalBuffers* bu
   if (cfg->num_groups <= 0 || !buf->group || !buf->results) return -5;
   const EvalArgs A = args_of(cfg, buf);
   hipLaunchKernelGGL(eval_reduce_kernel, dim3((unsigned)(cfg->num_groups * (NM + 1))), dim3(RT), 0, (hipStream_t)stream, A);
+  return hipGetLastError() == hipSuccess ? 0 : -20;
+}
+
+namespace {
+int check(const Go1BehaviourConfig* cfg, const Go1BehaviourBuffers* buf) {
+  if (!cfg || !buf || cfg->num_envs <= 0) return -1;
+  if (!buf->count || !buf->sum || !buf->sumsq || !buf->min || !buf->max || !buf->nonfinite || !buf->prev_contact || !buf->stride_steps ||
+      !buf->stance_steps || !buf->swing_peak) return -2;
+  return 0;
+}
+BehaviourArgs args_of(const Go1BehaviourConfig* cfg, const Go1BehaviourBuffers* buf) { BehaviourArgs A; A.c = *cfg; A.b = *buf; return A; }
+}  // namespace
+
+extern "C" int go1eval_behaviour_clear(const Go1BehaviourConfig* cfg, const Go1BehaviourBuffers* buf, void* stream) {
+  if (int rc = check(cfg, buf)) return rc;
+  const BehaviourArgs A = args_of(cfg, buf);
+  hipLaunchKernelGGL(behaviour_clear_kernel, env_grid(cfg->num_envs), dim3(ACC_THREADS), 0, (hipStream_t)stream, A);
+  return hipGetLastError() == hipSuccess ? 0 : -20;
+}
+
+extern "C" int go1eval_behaviour_accumulate(const Go1BehaviourConfig* cfg, const Go1BehaviourBuffers* buf, void* stream) {
+  if (int rc = check(cfg, buf)) return rc;
+  if (!buf->commands || !buf->root_states || !buf->contact_forces || !buf->foot_positions || !buf->foot_velocities ||
+      !buf->desired_contact_states || !buf->foot_indices || !buf->last_actions || !buf->last_last_actions || !buf->reset_buf ||
+      !buf->episode_length_buf) return -3;
+  if (buf->measured_heights && cfg->num_height_points <= 0) return -4;
+  if (cfg->num_commands < 12 || !(cfg->dt > 0.0f)) return -6;
+  const BehaviourArgs A = args_of(cfg, buf);
+  hipLaunchKernelGGL(behaviour_accumulate_kernel, env_grid(cfg->num_envs), dim3(ACC_THREADS), 0, (hipStream_t)stream, A);
+  return hipGetLastError() == hipSuccess ? 0 : -20;
+}
+
+extern "C" int go1eval_behaviour_reduce(const Go1BehaviourConfig* cfg, const Go1BehaviourBuffers* buf, void* stream) {
+  if (int rc = check(cfg, buf)) return rc;
+  if (cfg->num_groups <= 0 || !buf->group || !buf->results) return -5;
+  const BehaviourArgs A = args_of(cfg, buf);
+  hipLaunchKernelGGL(behaviour_reduce_kernel, dim3((unsigned)(cfg->num_groups * NB)), dim3(RT), 0, (hipStream_t)stream, A);
   return hipGetLastError() == hipSuccess ? 0 : -20;
 }
 

@@ -148,6 +148,7 @@ class LeggedRobot(BaseTask):
         self._render = None               # go1render_host.Go1Render, created by the first start_recording() / render()
         self._frames = [[], []]           # per camera: the last complete recording handed out
         self._metrics = None              # go1eval_host.Go1Eval, created by the first start_metrics()
+        self._behaviour = None            # go1eval_host.Go1Behaviour, created by the first start_metrics(behaviour=True)
         if eval_cfg is not None:          # reference legged_robot.py:41-42
             self._parse_cfg(eval_cfg)
         self._parse_cfg(cfg)
@@ -440,6 +441,8 @@ class LeggedRobot(BaseTask):
         self._record_step()
         if self._metrics is not None and self._metrics.armed:
             self._metrics.accumulate()
+            if self._behaviour is not None and self._behaviour.armed:
+                self._behaviour.accumulate()
         if self._curriculum_sync and (self.common_step_counter + 1) % self.sim_config.curriculum_update_interval == 0:
             # ONE exchange for the last `curriculum_update_interval` steps' success counts (a slot per step), then the per-step
             # updates in order: every rank applies what a single process over the concatenated shards would
@@ -575,33 +578,49 @@ class LeggedRobot(BaseTask):
     # ---- evaluation metrics (reference go1_gym_learn/eval_metrics/metrics.py, called by the host after every step there):
     # libgo1eval folds the ten scalar metrics of every environment into device accumulators (include/go1eval.h).  While metrics
     # are armed step() enqueues one more launch, after the simulator's and the recorder's; otherwise none, and the library is
-    # never imported.
+    # never imported.  start_metrics(behaviour=True) arms the library's second table as well (gait and behaviour tracking): one
+    # further launch per step.
     def _need_gpu_metrics(self, what):
         if self.buffers.device.type != "cuda":
             raise NotImplementedError(f"{what}(): the metrics are a HIP library; this simulator's buffers are not on a GPU")
 
-    def start_metrics(self, groups, warmup_steps=0):
+    def start_metrics(self, groups, warmup_steps=0, behaviour=False):
         """begin a measurement: `groups` = one int per environment (the row of the result table it counts towards, -1 = not
-        evaluated); steps with episode_length_buf <= warmup_steps count towards no metric"""
+        evaluated); steps with episode_length_buf <= warmup_steps count towards no metric.  behaviour=True also arms the
+        behaviour table (gait, body height, attitude, foot placement and stride tracking): one more launch per step"""
         self._need_gpu_metrics("start_metrics")
         if self._metrics is None:
             import go1eval_host
             self._metrics = go1eval_host.Go1Eval(self.sim_config, self.buffers)
         self._metrics.arm(groups, warmup_steps)
+        if behaviour:
+            if self._behaviour is None:
+                import go1eval_host
+                self._behaviour = go1eval_host.Go1Behaviour(self.sim_config, self.buffers, self.dt)
+            self._behaviour.arm(groups, warmup_steps)
+        elif self._behaviour is not None:
+            self._behaviour.disarm()
+            self._behaviour.table = None          # a measurement without the behaviour table reads none
 
     def stop_metrics(self):
         """stop folding steps; what was measured stays readable"""
         self._need_gpu_metrics("stop_metrics")
         if self._metrics is not None:
             self._metrics.disarm()
+        if self._behaviour is not None:
+            self._behaviour.disarm()
 
     def read_metrics(self):
         """{metric name: (groups, 6) array of count, mean, std, min, max, nonfinite; "groups": (groups, 5) array of envs, steps,
-        episodes_terminated, episodes_timed_out, fall_rate}: one reduction launch and one device-to-host copy"""
+        episodes_terminated, episodes_timed_out, fall_rate}: one reduction launch and one device-to-host copy.  After
+        start_metrics(behaviour=True) also "behaviour": {behaviour metric name: (groups, 6) array}, by one more of each"""
         self._need_gpu_metrics("read_metrics")
         if self._metrics is None:
             raise RuntimeError("read_metrics(): start_metrics() was never called")
-        return self._metrics.results()
+        res = self._metrics.results()
+        if self._behaviour is not None and self._behaviour.table is not None:
+            res["behaviour"] = self._behaviour.results()
+        return res
 
     def render(self, mode="rgb_array"):
         """reference :1612-1620: env 0 from its recording camera, now: (240, 360, 4) uint8 RGBA"""

@@ -36,7 +36,30 @@ class Go1EvalBuffers(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in _INPUTS + _ACCUMULATORS + _PER_ENV + ["group", "results"]]
 
 
-EXPORTED_SYMBOLS = ["go1eval_clear", "go1eval_accumulate", "go1eval_reduce", "go1eval_version"]
+# ---- the behaviour table (gait and behaviour tracking; include/go1eval.h, second kernel family)
+BEHAVIOUR_NAMES = ["contact_match", "body_height_err", "orientation_err", "feet_clearance", "raibert_heuristic", "feet_slip",
+                   "action_rate", "step_frequency_err", "duty_factor_err", "swing_height_err"]       # enum Go1BehaviourMetric
+STRIDE_NAMES = BEHAVIOUR_NAMES[7:]            # folded at a touchdown, not every step
+NUM_BEHAVIOUR = 10
+
+
+class Go1BehaviourConfig(ctypes.Structure):
+    _fields_ = [("num_envs", ctypes.c_int32), ("num_commands", ctypes.c_int32), ("num_height_points", ctypes.c_int32),
+                ("warmup_steps", ctypes.c_int32), ("num_groups", ctypes.c_int32), ("dt", ctypes.c_float),
+                ("base_height_target", ctypes.c_float)]
+
+
+_BEHAVIOUR_INPUTS = ["commands", "root_states", "measured_heights", "contact_forces", "foot_positions", "foot_velocities",
+                     "desired_contact_states", "foot_indices", "last_actions", "last_last_actions", "reset_buf", "episode_length_buf"]
+_STRIDE_STATE = ["prev_contact", "stride_steps", "stance_steps", "swing_peak"]
+
+
+class Go1BehaviourBuffers(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in _BEHAVIOUR_INPUTS + _ACCUMULATORS + _STRIDE_STATE + ["group", "results"]]
+
+
+EXPORTED_SYMBOLS = ["go1eval_clear", "go1eval_accumulate", "go1eval_reduce", "go1eval_version",
+                    "go1eval_behaviour_clear", "go1eval_behaviour_accumulate", "go1eval_behaviour_reduce"]
 
 _lib = None
 
@@ -58,6 +81,10 @@ def load_library(path=None):
     lib = ctypes.CDLL(p)
     cfg_p, buf_p = ctypes.POINTER(Go1EvalConfig), ctypes.POINTER(Go1EvalBuffers)
     for fn in ("go1eval_clear", "go1eval_accumulate", "go1eval_reduce"):
+        getattr(lib, fn).argtypes = [cfg_p, buf_p, ctypes.c_void_p]
+        getattr(lib, fn).restype = ctypes.c_int
+    cfg_p, buf_p = ctypes.POINTER(Go1BehaviourConfig), ctypes.POINTER(Go1BehaviourBuffers)
+    for fn in ("go1eval_behaviour_clear", "go1eval_behaviour_accumulate", "go1eval_behaviour_reduce"):
         getattr(lib, fn).argtypes = [cfg_p, buf_p, ctypes.c_void_p]
         getattr(lib, fn).restype = ctypes.c_int
     lib.go1eval_version.restype = ctypes.c_char_p
@@ -145,3 +172,75 @@ def table_to_dict(table):
     out = {name: table[:, m, :].copy() for m, name in enumerate(METRIC_NAMES)}
     out["groups"] = table[:, NUM_METRICS, :len(GROUP_FIELD_NAMES)].copy()
     return out
+
+
+_STRIDE_DTYPES = {"prev_contact": torch.uint8, "stride_steps": torch.int32, "stance_steps": torch.int32, "swing_peak": torch.float32}
+
+
+class Go1Behaviour:
+    """The behaviour table of one simulator instance, beside `Go1Eval`: it owns its accumulators and the per-foot stride state.
+    S: the simulator's Go1SimConfig, buffers: its SimBuffers (device tensors), dt: the policy step in seconds."""
+
+    def __init__(self, S, buffers, dt, lib=None):
+        self.lib = lib if lib is not None else load_library()
+        self.buffers = buffers
+        self.device = buffers.device
+        N = self.num_envs = int(S.num_envs)
+        c = self.cfg = Go1BehaviourConfig()
+        c.num_envs, c.num_commands, c.dt, c.base_height_target = N, int(S.num_commands), float(dt), float(S.base_height_target)
+        self.measure_heights = bool(S.measure_heights)
+        c.num_height_points = int(buffers.measured_heights.shape[0]) if self.measure_heights else 0
+        self.acc = {n: torch.zeros(NUM_BEHAVIOUR, N, dtype=dt_, device=self.device) for n, dt_ in _ACC_DTYPES.items()}
+        self.stride = {n: torch.zeros(4, N, dtype=dt_, device=self.device) for n, dt_ in _STRIDE_DTYPES.items()}
+        self.group = torch.full((N,), -1, dtype=torch.int32, device=self.device)
+        self.table = None
+        self.armed = False
+        self.buf = Go1BehaviourBuffers()
+        self._refresh()
+
+    def _refresh(self):
+        b, B = self.buf, self.buffers
+        for n in _BEHAVIOUR_INPUTS:
+            setattr(b, n, getattr(B, n).data_ptr())
+        if not self.measure_heights:
+            b.measured_heights = None
+        for n, t in list(self.acc.items()) + list(self.stride.items()):
+            setattr(b, n, t.data_ptr())
+        b.group = self.group.data_ptr()
+        b.results = self.table.data_ptr() if self.table is not None else None
+
+    _stream, _check = Go1Eval._stream, Go1Eval._check
+
+    def _call(self, name):
+        self._check(getattr(self.lib, name)(ctypes.byref(self.cfg), ctypes.byref(self.buf), self._stream()), name)
+
+    def arm(self, groups, warmup_steps=0):
+        """start a measurement (as Go1Eval.arm): empties the accumulators and forgets every stride"""
+        g = torch.as_tensor(groups).to(torch.int32).reshape(-1)
+        assert g.numel() == self.num_envs, (g.numel(), self.num_envs)
+        G = int(g.max()) + 1
+        assert G >= 1, "no environment carries a group id >= 0"
+        self.group.copy_(g)
+        self.cfg.num_groups, self.cfg.warmup_steps = G, int(warmup_steps)
+        self.table = torch.zeros(G, NUM_BEHAVIOUR, NUM_FIELDS, dtype=torch.float64, device=self.device)
+        self._refresh()
+        self._call("go1eval_behaviour_clear")
+        self.armed = True
+
+    def accumulate(self):
+        """after a step: fold it and advance the stride state (one launch, no sync)"""
+        self._call("go1eval_behaviour_accumulate")
+
+    def disarm(self):
+        self.armed = False
+
+    def reduce(self):
+        """the result table [G][NUM_BEHAVIOUR][NUM_FIELDS] as a device tensor (one launch, no sync)"""
+        assert self.table is not None, "arm() first"
+        self._call("go1eval_behaviour_reduce")
+        return self.table
+
+    def results(self):
+        """{behaviour metric name: (G, 6) array with the columns FIELD_NAMES}: one launch and one device-to-host copy"""
+        table = self.reduce().cpu().numpy()
+        return {name: table[:, m, :].copy() for m, name in enumerate(BEHAVIOUR_NAMES)}
