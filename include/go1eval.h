@@ -111,6 +111,66 @@
  * go1eval_behaviour_clear: accumulators as go1eval_clear; prev_contact = 2, stride_steps = -1, stance_steps = 0, swing_peak = -inf.
  * go1eval_behaviour_reduce: the metric rows of go1eval_reduce, the same fixed combination order (the same device function), into
  * results[num_groups][GO1EVAL_NUM_BEHAVIOUR][GO1EVAL_NUM_FIELDS].  There is no group row; the first table has it.
+ *
+ * ---- the trace and the step response (third kernel family) --------------------------------------------------------------------
+ * The two tables measure steady state.  The trace is a per-step time series of GO1EVAL_NUM_TRACE fp32 channels of K chosen
+ * environments, written on the device by one launch per step; the response analysis turns a trace that holds ONE command switch
+ * into rise time, overshoot, settling time, steady-state error and integrated error per environment, reduced per group by the
+ * tables' fixed-order reduction.  Replaces the per-step host reads of the reference's scripts/play.py (base_lin_vel[0, 0] and
+ * dof_pos[0, :] copied to the host after every one of its 250 steps).
+ *
+ * Channels (index = Go1TraceChannel), the value after a step:
+ *    0 lin_vel_x          base_lin_vel[0]                  6 cmd_lin_vel_x    commands[0]
+ *    1 lin_vel_y          base_lin_vel[1]                  7 cmd_lin_vel_y    commands[1]
+ *    2 ang_vel_yaw        base_ang_vel[2]                  8 cmd_ang_vel_yaw  commands[2]
+ *    3 base_height        the metric base_height above     9 cmd_base_height  commands[3] + base_height_target (one fp32 add)
+ *    4 contact_match      the behaviour table's           10 max_torques      the metric max_torques above
+ *    5 power_consumption  the metric power_consumption    11 reset            reset_buf != 0 ? 1 : 0
+ *   12..23 dof_pos_0..11  dof_pos[j]
+ *   Channels 3, 5 and 10 are the first table's expressions (the same fp32 terms, the same fp64 carry, rounded once) and channel 4
+ *   is the behaviour table's, evaluated on EVERY step: the trace has no warm-up and no reset rule.  A reset step is recorded as
+ *   the buffers stand (the old episode's velocities with the new episode's pose); channel 11 marks it.
+ *
+ * go1eval_trace_record(cfg, buf, row, stream): one launch, one thread per traced environment k in [0, K), K = num_traced.  It
+ *   reads environment env_ids[k]; env_ids == NULL means k itself and needs K == N.  It writes trace[(row * 24 + c) * K + k] for
+ *   the 24 channels c, so a wavefront's stores of one channel are one contiguous run.  An id outside [0, N) writes NaN to its 24
+ *   values.  `row` is a host argument (the caller counts its own launches): row < 0 or row >= capacity is refused before the
+ *   launch with a code of its own (-7), and nothing is written.
+ *
+ * go1eval_response(cfg, buf, stream): one launch, one thread per traced environment, a pure function of the trace.  rows = the
+ *   recorded rows, s0 = switch_row (the first row recorded after the command changed: the state one policy step after the
+ *   switch), w = smooth, end = rows.  Refused before the launch (-9) unless 1 <= w <= pre + 1, pre <= s0 < rows, hold >= 1,
+ *   tail >= 1, max(hold, tail) <= rows - s0, dt > 0 and band > 0; (-10) unless 1 <= num_signals <= GO1EVAL_MAX_SIGNALS, every
+ *   y_channel is in [0, 24) and every r_channel is below 24 (negative: none).  c[t] below is channel c of this environment at row t.
+ *   Every operation that is not marked fp64 is an fp32 operation on fp32 values; 0.1 and 1e-6 are fp32 constants.
+ *   1. Status.  1: some row in [s0 - pre, end) has channel 11 != 0 (the robot fell or timed out inside the window; a NaN, the
+ *      trace of an id outside [0, N), is != 0).  Otherwise 2: some signal with r_channel >= 0 has a row t in [s0, end) with
+ *      r[t] != r1 = r[s0], or a row t in [s0 - pre, s0) with r[t] != r0 = r[s0 - 1] (the command was not held).  Otherwise 0.
+ *      With status != 0 every value of every signal is NaN.
+ *   2. Per signal {y_channel, r_channel, fixed_target, fixed_scale}: r1 = r[s0], r0 = r[s0 - 1] (r0 = r1 when s0 == 0);
+ *      r_channel < 0: r1 = fixed_target and r0 = r1.  Scale D = fixed_scale if fixed_scale > 0, else |r1 - r0|.  D < 1e-6: all
+ *      seven values are NaN (there is no step on this signal).  Direction sgn = +1 if r1 >= r0, else -1.
+ *   3. Smoothed signal: ys(t) = the mean of y over rows t - w + 1 .. t: added in an fp64 carry in ascending row order, divided
+ *      by (double)w in fp64, rounded to fp32 once.  e(t) = ys(t) - r1.
+ *   4. Seven values (index = Go1ResponseMetric), t over [s0, end) in ascending order:
+ *      reached           1 if some t has |e(t)| <= 0.1 * D, else 0
+ *      rise_time         (float)(t_r - s0 + 1) * dt for the first such t = t_r; NaN when not reached
+ *      overshoot         the fold of fmaxf over sgn * e(t) / D, starting from 0: max(0, the largest excursion past the target) / D
+ *      settled           t_v = the last t with |e(t)| > band * D, t_s = t_v + 1 (s0 if there is none); 1 if t_s <= end - hold, else 0
+ *      settling_time     (float)(t_s - s0 + 1) * dt; NaN when not settled
+ *      steady_state_err  the mean over rows [end - tail, end) of the raw y[t] - r1, signed: the fp32 differences added in an
+ *                        fp64 carry, divided by (double)tail in fp64, rounded to fp32 once
+ *      iae               dt * the sum over [s0, end) of |y[t] - r1|, raw: the fp32 terms added in an fp64 carry, multiplied by
+ *                        (double)dt in fp64, rounded to fp32 once
+ *      The box filter delays ys by about (w - 1) / 2 rows, and that delay is inside rise_time and settling_time.
+ *   5. Outputs: values[(s * 7 + m) * K + k] (fp32) for signal s and value m, and status[k] (int32).  One writer each, no atomics.
+ *
+ * go1eval_response_reduce(cfg, buf, stream): results[num_groups][num_signals * 7 + 1][GO1EVAL_NUM_FIELDS] over the traced
+ *   environments with group[k] == g (-1 or any id outside the range = not evaluated).  Row s * 7 + m is the metric row of
+ *   go1eval_reduce (the same device function, the same fixed combination order) over per-environment accumulators that folded the
+ *   one value values[s][m][k] by the folding rule above: a non-finite value counts in nonfinite and enters nothing else; a finite
+ *   value v has count 1, sum v, sumsq v * v (fp64), min = max = v.  The last row of a group: traced environments, environments
+ *   with status 0, with status 1, with status 2, 0, 0 (sums in the same fixed order).
  */
 #ifndef GO1EVAL_H_INCLUDED
 #define GO1EVAL_H_INCLUDED
@@ -243,6 +303,90 @@ int go1eval_behaviour_accumulate(const Go1BehaviourConfig* cfg, const Go1Behavio
 
 /* at the end: the result table from the accumulators (which it leaves as they are).  One launch. */
 int go1eval_behaviour_reduce(const Go1BehaviourConfig* cfg, const Go1BehaviourBuffers* buf, void* stream);
+
+/* ---- the trace and the step response ------------------------------------------------------------------------------------------ */
+#define GO1EVAL_NUM_TRACE 24
+#define GO1EVAL_NUM_RESPONSE 7
+#define GO1EVAL_MAX_SIGNALS 8
+
+enum Go1TraceChannel {
+  GO1TRACE_LIN_VEL_X = 0, GO1TRACE_LIN_VEL_Y = 1, GO1TRACE_ANG_VEL_YAW = 2, GO1TRACE_BASE_HEIGHT = 3, GO1TRACE_CONTACT_MATCH = 4,
+  GO1TRACE_POWER_CONSUMPTION = 5, GO1TRACE_CMD_LIN_VEL_X = 6, GO1TRACE_CMD_LIN_VEL_Y = 7, GO1TRACE_CMD_ANG_VEL_YAW = 8,
+  GO1TRACE_CMD_BASE_HEIGHT = 9, GO1TRACE_MAX_TORQUES = 10, GO1TRACE_RESET = 11, GO1TRACE_DOF_POS_0 = 12, GO1TRACE_DOF_POS_1 = 13,
+  GO1TRACE_DOF_POS_2 = 14, GO1TRACE_DOF_POS_3 = 15, GO1TRACE_DOF_POS_4 = 16, GO1TRACE_DOF_POS_5 = 17, GO1TRACE_DOF_POS_6 = 18,
+  GO1TRACE_DOF_POS_7 = 19, GO1TRACE_DOF_POS_8 = 20, GO1TRACE_DOF_POS_9 = 21, GO1TRACE_DOF_POS_10 = 22, GO1TRACE_DOF_POS_11 = 23
+};
+enum Go1ResponseMetric {
+  GO1RESPONSE_REACHED = 0, GO1RESPONSE_RISE_TIME = 1, GO1RESPONSE_OVERSHOOT = 2, GO1RESPONSE_SETTLED = 3, GO1RESPONSE_SETTLING_TIME = 4,
+  GO1RESPONSE_STEADY_STATE_ERR = 5, GO1RESPONSE_IAE = 6
+};
+/* columns of a group's own row (row num_signals * GO1EVAL_NUM_RESPONSE) of the response table */
+enum Go1ResponseGroupField { GO1RESPONSE_G_ENVS = 0, GO1RESPONSE_G_OK = 1, GO1RESPONSE_G_RESET = 2, GO1RESPONSE_G_NOT_HELD = 3 };
+
+typedef struct Go1TraceConfig {
+  int32_t num_envs;            /* N of the simulator's SoA buffers */
+  int32_t num_traced;          /* K: traced environments (== num_envs when env_ids is NULL) */
+  int32_t capacity;            /* rows the trace buffer holds */
+  int32_t num_height_points;   /* rows of measured_heights (ignored when it is NULL) */
+  float base_height_target;    /* m, the reference's rewards.base_height_target */
+} Go1TraceConfig;
+
+typedef struct Go1TraceBuffers {
+  const float* base_lin_vel;            /* [3][N] */
+  const float* base_ang_vel;            /* [3][N] */
+  const float* commands;                /* [>= 4][N] */
+  const float* root_states;             /* [13][N]; row 2 is read */
+  const float* measured_heights;        /* [num_height_points][N] or NULL (the ground is 0) */
+  const float* contact_forces;          /* [17 * 3][N]; the feet are bodies 4, 8, 12, 16 */
+  const float* desired_contact_states;  /* [4][N] */
+  const float* torques;                 /* [12][N] */
+  const float* dof_vel;                 /* [12][N] */
+  const float* dof_pos;                 /* [12][N] */
+  const uint8_t* reset_buf;             /* [N] */
+  const int32_t* env_ids;               /* [K] or NULL (environment k itself) */
+  float* trace;                         /* [capacity][GO1EVAL_NUM_TRACE][K] */
+} Go1TraceBuffers;
+
+typedef struct Go1ResponseSignal {
+  int32_t y_channel;           /* the measured channel */
+  int32_t r_channel;           /* the channel that carries its target, or < 0: fixed_target */
+  float fixed_target;          /* the target when r_channel < 0 */
+  float fixed_scale;           /* > 0: the scale D; otherwise D = |r1 - r0| */
+} Go1ResponseSignal;
+
+typedef struct Go1ResponseConfig {
+  int32_t num_traced;          /* K of the trace */
+  int32_t rows;                /* recorded rows (<= the trace's capacity) */
+  int32_t switch_row;          /* s0: the first row recorded after the command changed */
+  int32_t pre;                 /* rows before s0 that the status rules cover */
+  int32_t smooth;              /* w: rows of the box filter */
+  int32_t hold;                /* rows at the end that have to stay inside the band for `settled` */
+  int32_t tail;                /* rows at the end that steady_state_err averages */
+  float band;                  /* the settling band, as a fraction of D */
+  float dt;                    /* s, the policy step */
+  int32_t num_signals;         /* S <= GO1EVAL_MAX_SIGNALS */
+  int32_t num_groups;          /* G of the result table (go1eval_response_reduce) */
+  Go1ResponseSignal signal[GO1EVAL_MAX_SIGNALS];
+} Go1ResponseConfig;
+
+typedef struct Go1ResponseBuffers {
+  const float* trace;          /* [rows][GO1EVAL_NUM_TRACE][K] */
+  float* values;               /* [num_signals][GO1EVAL_NUM_RESPONSE][K] */
+  int32_t* status;             /* [K] */
+  /* go1eval_response_reduce */
+  const int32_t* group;        /* [K] */
+  double* results;             /* [num_groups][num_signals * GO1EVAL_NUM_RESPONSE + 1][GO1EVAL_NUM_FIELDS] */
+} Go1ResponseBuffers;
+
+/* after a simulator step: row `row` of the trace.  One launch, one thread per traced environment.  row outside [0, capacity): -7,
+ * nothing is written.  env_ids == NULL with num_traced != num_envs: -8. */
+int go1eval_trace_record(const Go1TraceConfig* cfg, const Go1TraceBuffers* buf, int32_t row, void* stream);
+
+/* the step response of every traced environment from the trace.  One launch.  Window refused: -9; signal refused: -10. */
+int go1eval_response(const Go1ResponseConfig* cfg, const Go1ResponseBuffers* buf, void* stream);
+
+/* the response table from values and status (which it leaves as they are).  One launch. */
+int go1eval_response_reduce(const Go1ResponseConfig* cfg, const Go1ResponseBuffers* buf, void* stream);
 
 /* "go1eval <version> (gfx950) go1-src:<16 hex digits of the source hash>" */
 const char* go1eval_version(void);

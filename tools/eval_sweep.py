@@ -12,6 +12,14 @@ The checkpoint directory holds `ac_weights_last.pt` (the Runner's state dict) or
 With `--behaviour` the sweep runs over the product of the `--axis NAME V1 V2 ...` command values instead (names:
 go1_gym_learn.eval_metrics.behaviour.COMMAND_INDEX), both tables are accumulated on the device, `<out>/eval/<preset>_behaviour.json`
 is written and the commanded-versus-realised table is printed.
+
+    python tools/eval_sweep.py --checkpoint RUN_DIR/checkpoints --out RUN_DIR --response --switch vx 0.5 1.0 1.5 --trace-envs 0 1
+
+With `--response` every environment holds the command `--switch NAME FROM TO [TO ...]` at FROM and is switched to one of the TO
+values (NAME: a name of COMMAND_INDEX, or `gait` with gait names); the trace around the switch is recorded and analysed on the
+device (go1_gym_learn.eval_metrics.response), `<out>/eval/<preset>_response.json` is written and the step-response table is
+printed and appended to `<out>/eval/<preset>_response.md`.  `--trace-envs I [I ...]` also writes those environments' traces to
+`<out>/eval/<preset>_trace.npz` and the velocity / joint-position figure of each to `<preset>_trace_env<I>.png`.
 Run on the GPU box."""
 import argparse
 import json
@@ -84,8 +92,45 @@ def parse_args(argv=None):
     ap.add_argument("--terrain", default=None, choices=["plane", "heightfield", "trimesh"])
     ap.add_argument("--behaviour", action="store_true", help="measure gait and behaviour tracking over the --axis product instead of the velocity grid")
     ap.add_argument("--axis", nargs="+", action="append", metavar=("NAME", "VALUE"), help="a behaviour command and its values; repeatable")
+    ap.add_argument("--response", action="store_true", help="measure the step response to the --switch of one command instead of the velocity grid")
+    ap.add_argument("--switch", nargs="+", metavar=("NAME", "VALUE"), help="the switched command, its value before and its values after")
+    ap.add_argument("--trace-envs", nargs="+", type=int, default=None, help="with --response: environments whose trace and figure are written")
     ap.add_argument("--out", required=True)
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if (a.switch or a.trace_envs) and not a.response:
+        ap.error("--switch and --trace-envs need --response")
+    if a.response and (not a.switch or len(a.switch) < 3):
+        ap.error("--response needs --switch NAME FROM TO [TO ...]")
+    return a
+
+
+def response_switch(a):
+    """(command, from value, [to values]) of the --switch option: gait names for `gait`, numbers otherwise"""
+    name, first, *rest = a.switch
+    if name == "gait":
+        return name, first, rest
+    return name, float(first), [float(v) for v in rest]
+
+
+def run_response(a, policy):
+    import numpy as np
+    from go1_gym_learn.eval_metrics import response
+    command, from_value, to_values = response_switch(a)
+    for preset in a.presets:
+        res = response.run_response_sweep(policy, preset, command, from_value, to_values, num_envs=a.envs, seed=a.seed, terrain=a.terrain,
+                                          trace_envs=a.trace_envs)
+        stem = os.path.join(a.out, "eval", preset)
+        with open(stem + "_response.json", "w") as f:
+            json.dump(response.response_to_json(res), f, indent=1)
+        text = f"### {preset}: {a.envs} environments, {command} {from_value} -> {to_values}, step response\n\n"
+        text += "\n\n".join(response.response_markdown_table(res, s) for s in res["signals"]) + "\n"
+        print(text)
+        with open(stem + "_response.md", "a") as f:
+            f.write(text + "\n")
+        if a.trace_envs:
+            np.savez(stem + "_trace.npz", **res["trace"])
+            for e in a.trace_envs:
+                response.plot_trace(res["trace"], e, f"{stem}_trace_env{e}.png", dt=res["dt"])
 
 
 def behaviour_axes(a):
@@ -108,6 +153,8 @@ def main(argv=None):
     policy = load_policy(a.checkpoint, "cuda:0")
     grid = dict(vx=a.vx, yaw=a.yaw, gait=[sweep.GAITS[g] for g in a.gaits])
     os.makedirs(os.path.join(a.out, "eval"), exist_ok=True)
+    if a.response:
+        return run_response(a, policy)
     if a.behaviour:
         from go1_gym_learn.eval_metrics import behaviour
         axes = behaviour_axes(a)

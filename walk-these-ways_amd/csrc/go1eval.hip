@@ -9,6 +9,9 @@
 // behaviour_accumulate_kernel / behaviour_reduce_kernel: the second table (gait and behaviour tracking), the same shapes: one
 // thread per environment that also carries the per-foot stride state ([4][N], one writer per word), and the metric-row reduction
 // shared with eval_reduce_kernel (reduce_metric_row).  tests/behaviour_ref.py is their fp64 model.
+// trace_record_kernel / response_kernel / response_reduce_kernel: the trace and the step response, the same shapes again: one
+// thread per traced environment; a channel of a trace row is [K] consecutive floats, so both the stores of the record and the
+// loads of the analysis (sequential over the rows per thread) are contiguous across a wavefront.  tests/response_ref.py is the model.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -84,6 +87,26 @@ __device__ __forceinline__ V3 quat_rotate(float x, float y, float z, float w, V3
 }
 __device__ __forceinline__ V3 quat_rotate_inverse(float x, float y, float z, float w, V3 v) { return quat_rotate(-x, -y, -z, w, v); }
 
+// the metric base_height: root z minus the mean of measured_heights (fp64 carry, one rounding: see the header); NULL: root z
+__device__ __forceinline__ float height_above_ground(const float* measured_heights, int num_height_points, int N, int e, float z) {
+  if (!measured_heights) return z;                    // mean of (z - 0) over one point
+  double s = 0.0;
+  for (int p = 0; p < num_height_points; p++) s += (double)(z - measured_heights[(size_t)p * N + e]);
+  return (float)s / (float)num_height_points;
+}
+
+// the metrics max_torques and power_consumption of one environment (power: fp64 carry over the fp32 products, one rounding)
+__device__ __forceinline__ void torque_figures(const float* torques, const float* dof_vel, int N, int e, float* tmax, float* power) {
+  float m = 0.f;
+  double psum = 0.0;
+  for (int j = 0; j < 12; j++) {
+    const float tq = torques[j * N + e];
+    m = fmaxf(m, fabsf(tq));
+    psum += (double)(tq * dof_vel[j * N + e]);
+  }
+  *tmax = m; *power = (float)psum;
+}
+
 }  // namespace
 
 extern "C" __global__ void __launch_bounds__(ACC_THREADS) eval_clear_kernel(const EvalArgs A) {
@@ -118,23 +141,10 @@ extern "C" __global__ void __launch_bounds__(ACC_THREADS) eval_accumulate_kernel
   fold(b, GO1EVAL_LIN_VEL_X, N, e, vx);
   fold(b, GO1EVAL_ANG_VEL_YAW, N, e, wz);
 
-  const float z = b.root_states[2 * N + e];
-  float height = z;                                   // measured_heights = NULL: mean of (z - 0) over one point
-  if (b.measured_heights) {
-    double s = 0.0;                                   // (fp64 carry, one rounding: see the header)
-    for (int p = 0; p < A.c.num_height_points; p++) s += (double)(z - b.measured_heights[(size_t)p * N + e]);
-    height = (float)s / (float)A.c.num_height_points;
-  }
-  fold(b, GO1EVAL_BASE_HEIGHT, N, e, height);
+  fold(b, GO1EVAL_BASE_HEIGHT, N, e, height_above_ground(b.measured_heights, A.c.num_height_points, N, e, b.root_states[2 * N + e]));
 
-  float tmax = 0.f;
-  double psum = 0.0;
-  for (int j = 0; j < 12; j++) {
-    const float tq = b.torques[j * N + e];
-    tmax = fmaxf(tmax, fabsf(tq));
-    psum += (double)(tq * b.dof_vel[j * N + e]);
-  }
-  const float power = (float)psum;
+  float tmax, power;
+  torque_figures(b.torques, b.dof_vel, N, e, &tmax, &power);
   fold(b, GO1EVAL_MAX_TORQUES, N, e, tmax);
   fold(b, GO1EVAL_POWER_CONSUMPTION, N, e, power);
 
@@ -241,12 +251,7 @@ extern "C" __global__ void __launch_bounds__(ACC_THREADS) behaviour_accumulate_k
   }
   fold(b, GO1EVAL_CONTACT_MATCH, N, e, 0.25f * (float)matches);
 
-  float height = base.z;
-  if (b.measured_heights) {
-    double s = 0.0;
-    for (int p = 0; p < A.c.num_height_points; p++) s += (double)(base.z - b.measured_heights[(size_t)p * N + e]);
-    height = (float)s / (float)A.c.num_height_points;
-  }
+  const float height = height_above_ground(b.measured_heights, A.c.num_height_points, N, e, base.z);
   fold(b, GO1EVAL_BODY_HEIGHT_ERR, N, e, height - (cmd_height + A.c.base_height_target));
 
   float sr, cr, sp, cp;
@@ -293,6 +298,163 @@ extern "C" __global__ void __launch_bounds__(RT) behaviour_reduce_kernel(const B
   __shared__ double lds[NF][RT];
   const int g = (int)blockIdx.x / NB, m = (int)blockIdx.x % NB;
   reduce_metric_row(A.b, g, m, A.c.num_envs, lds, A.b.results + ((size_t)g * NB + m) * NF);
+}
+
+// ---- the trace and the step response --------------------------------------------------------------------------------------------
+constexpr int NT = GO1EVAL_NUM_TRACE, NR = GO1EVAL_NUM_RESPONSE;
+
+struct TraceArgs {
+  Go1TraceConfig c;
+  Go1TraceBuffers b;
+  int row;
+};
+
+struct ResponseArgs {
+  Go1ResponseConfig c;
+  Go1ResponseBuffers b;
+};
+
+extern "C" __global__ void __launch_bounds__(ACC_THREADS) trace_record_kernel(const TraceArgs A) {
+  const int N = A.c.num_envs, K = A.c.num_traced;
+  const int k = (int)(blockIdx.x * ACC_THREADS + threadIdx.x);
+  if (k >= K) return;
+  const Go1TraceBuffers& b = A.b;
+  float* out = b.trace + (size_t)A.row * NT * K + k;             // channel c at out[c * K]: consecutive k, consecutive floats
+  const int e = b.env_ids ? b.env_ids[k] : k;
+  if (e < 0 || e >= N) {
+    for (int c = 0; c < NT; c++) out[(size_t)c * K] = NAN;
+    return;
+  }
+  const auto row = [N, e](const float* p, int r) { return p[(size_t)r * N + e]; };
+  out[(size_t)GO1TRACE_LIN_VEL_X * K] = row(b.base_lin_vel, 0);
+  out[(size_t)GO1TRACE_LIN_VEL_Y * K] = row(b.base_lin_vel, 1);
+  out[(size_t)GO1TRACE_ANG_VEL_YAW * K] = row(b.base_ang_vel, 2);
+  out[(size_t)GO1TRACE_BASE_HEIGHT * K] = height_above_ground(b.measured_heights, A.c.num_height_points, N, e, row(b.root_states, 2));
+  int matches = 0;
+  for (int f = 0; f < 4; f++) {
+    const bool contact = row(b.contact_forces, (4 + 4 * f) * 3 + 2) > (float)GO1EVAL_CONTACT_FORCE;
+    matches += contact == (row(b.desired_contact_states, f) > 0.5f) ? 1 : 0;
+  }
+  out[(size_t)GO1TRACE_CONTACT_MATCH * K] = 0.25f * (float)matches;
+  float tmax, power;
+  torque_figures(b.torques, b.dof_vel, N, e, &tmax, &power);
+  out[(size_t)GO1TRACE_POWER_CONSUMPTION * K] = power;
+  out[(size_t)GO1TRACE_CMD_LIN_VEL_X * K] = row(b.commands, 0);
+  out[(size_t)GO1TRACE_CMD_LIN_VEL_Y * K] = row(b.commands, 1);
+  out[(size_t)GO1TRACE_CMD_ANG_VEL_YAW * K] = row(b.commands, 2);
+  out[(size_t)GO1TRACE_CMD_BASE_HEIGHT * K] = row(b.commands, 3) + A.c.base_height_target;
+  out[(size_t)GO1TRACE_MAX_TORQUES * K] = tmax;
+  out[(size_t)GO1TRACE_RESET * K] = b.reset_buf[e] != 0 ? 1.0f : 0.0f;
+  for (int j = 0; j < 12; j++) out[(size_t)(GO1TRACE_DOF_POS_0 + j) * K] = row(b.dof_pos, j);
+}
+
+extern "C" __global__ void __launch_bounds__(ACC_THREADS) response_kernel(const ResponseArgs A) {
+  const Go1ResponseConfig& c = A.c;
+  const int K = c.num_traced;
+  const int k = (int)(blockIdx.x * ACC_THREADS + threadIdx.x);
+  if (k >= K) return;
+  const float* trace = A.b.trace;
+  const auto at = [trace, K, k](int t, int ch) { return trace[((size_t)t * NT + ch) * K + k]; };   // consecutive k, consecutive floats
+  const int s0 = c.switch_row, end = c.rows, w = c.smooth;
+
+  int status = 0;
+  for (int t = s0 - c.pre; t < end; t++) {
+    if (at(t, GO1TRACE_RESET) != 0.0f) status = 1;
+  }
+  if (status == 0) {
+    for (int s = 0; s < c.num_signals; s++) {
+      const int rc = c.signal[s].r_channel;
+      if (rc < 0) continue;
+      const float r1 = at(s0, rc), r0 = s0 > 0 ? at(s0 - 1, rc) : r1;
+      for (int t = s0 - c.pre; t < end; t++) {
+        if (at(t, rc) != (t < s0 ? r0 : r1)) status = 2;
+      }
+    }
+  }
+  A.b.status[k] = status;
+
+  for (int s = 0; s < c.num_signals; s++) {
+    float* out = A.b.values + (size_t)s * NR * K + k;
+    const Go1ResponseSignal sig = c.signal[s];
+    float r1 = sig.fixed_target, r0 = sig.fixed_target;
+    if (sig.r_channel >= 0) { r1 = at(s0, sig.r_channel); r0 = s0 > 0 ? at(s0 - 1, sig.r_channel) : r1; }
+    const float D = sig.fixed_scale > 0.0f ? sig.fixed_scale : fabsf(r1 - r0);
+    if (status != 0 || D < 1e-6f) {
+      for (int m = 0; m < NR; m++) out[(size_t)m * K] = NAN;
+      continue;
+    }
+    const float sgn = r1 >= r0 ? 1.0f : -1.0f;
+    const float near = 0.1f * D, inside = c.band * D;
+    int t_r = -1, t_s = s0;
+    float over = 0.0f;
+    double tail_sum = 0.0, abs_sum = 0.0;
+    for (int t = s0; t < end; t++) {
+      double sum = 0.0;
+      for (int u = t - w + 1; u <= t; u++) sum += (double)at(u, sig.y_channel);
+      const float ys = (float)(sum / (double)w);
+      const float err = ys - r1;
+      if (t_r < 0 && fabsf(err) <= near) t_r = t;
+      over = fmaxf(over, sgn * err / D);
+      if (fabsf(err) > inside) t_s = t + 1;
+      const float raw = at(t, sig.y_channel) - r1;
+      abs_sum += (double)fabsf(raw);
+      if (t >= end - c.tail) tail_sum += (double)raw;
+    }
+    const bool settled = t_s <= end - c.hold;
+    out[(size_t)GO1RESPONSE_REACHED * K] = t_r >= 0 ? 1.0f : 0.0f;
+    out[(size_t)GO1RESPONSE_RISE_TIME * K] = t_r >= 0 ? (float)(t_r - s0 + 1) * c.dt : NAN;
+    out[(size_t)GO1RESPONSE_OVERSHOOT * K] = over;
+    out[(size_t)GO1RESPONSE_SETTLED * K] = settled ? 1.0f : 0.0f;
+    out[(size_t)GO1RESPONSE_SETTLING_TIME * K] = settled ? (float)(t_s - s0 + 1) * c.dt : NAN;
+    out[(size_t)GO1RESPONSE_STEADY_STATE_ERR * K] = (float)(tail_sum / (double)c.tail);
+    out[(size_t)GO1RESPONSE_IAE * K] = (float)((double)c.dt * abs_sum);
+  }
+}
+
+namespace {
+// values[s][m][K] seen as the accumulators of an environment that folded the one value: what reduce_metric_row reads
+struct FoldedOnce {
+  struct Count { const float* v; __device__ uint32_t operator[](size_t i) const { return isfinite(v[i]) ? 1u : 0u; } };
+  struct Nonfinite { const float* v; __device__ uint32_t operator[](size_t i) const { return isfinite(v[i]) ? 0u : 1u; } };
+  struct Sum { const float* v; __device__ double operator[](size_t i) const { return isfinite(v[i]) ? (double)v[i] : 0.0; } };
+  struct Sumsq { const float* v; __device__ double operator[](size_t i) const { return isfinite(v[i]) ? (double)v[i] * (double)v[i] : 0.0; } };
+  struct Value { const float* v; __device__ float operator[](size_t i) const { return v[i]; } };
+  const int32_t* group;
+  Count count; Nonfinite nonfinite; Sum sum; Sumsq sumsq; Value min, max;
+};
+}  // namespace
+
+extern "C" __global__ void __launch_bounds__(RT) response_reduce_kernel(const ResponseArgs A) {
+  __shared__ double lds[NF][RT];
+  const int K = A.c.num_traced, rows = A.c.num_signals * NR + 1;
+  const int t = (int)threadIdx.x;
+  const int g = (int)blockIdx.x / rows, m = (int)blockIdx.x % rows;
+  const Go1ResponseBuffers& b = A.b;
+  double* out = b.results + ((size_t)g * rows + m) * NF;
+  if (m != rows - 1) {
+    const float* v = b.values;
+    const FoldedOnce once = {b.group, {v}, {v}, {v}, {v}, {v}, {v}};
+    reduce_metric_row(once, g, m, K, lds, out);
+    return;
+  }
+  // the group's own row: a0 traced environments, a1 status 0, a2 status 1, a3 status 2
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+  for (int e = t; e < K; e += RT) {
+    if (b.group[e] != g) continue;
+    const int st = b.status[e];
+    a0 += 1.0; a1 += st == 0 ? 1.0 : 0.0; a2 += st == 1 ? 1.0 : 0.0; a3 += st == 2 ? 1.0 : 0.0;
+  }
+  lds[0][t] = a0; lds[1][t] = a1; lds[2][t] = a2; lds[3][t] = a3;
+  __syncthreads();
+  for (int s = RT / 2; s > 0; s >>= 1) {
+    if (t < s) {
+      for (int f = 0; f < 4; f++) lds[f][t] += lds[f][t + s];
+    }
+    __syncthreads();
+  }
+  if (t != 0) return;
+  out[GO1RESPONSE_G_ENVS] = lds[0][0]; out[GO1RESPONSE_G_OK] = lds[1][0]; out[GO1RESPONSE_G_RESET] = lds[2][0];
+  out[GO1RESPONSE_G_NOT_HELD] = lds[3][0]; out[4] = 0.0; out[5] = 0.0;
 }
 
 namespace {
@@ -365,6 +527,52 @@ extern "C" int go1eval_behaviour_reduce(const Go1BehaviourConfig* cfg, const Go1
   if (cfg->num_groups <= 0 || !buf->group || !buf->results) return -5;
   const BehaviourArgs A = args_of(cfg, buf);
   hipLaunchKernelGGL(behaviour_reduce_kernel, dim3((unsigned)(cfg->num_groups * NB)), dim3(RT), 0, (hipStream_t)stream, A);
+  return hipGetLastError() == hipSuccess ? 0 : -20;
+}
+
+extern "C" int go1eval_trace_record(const Go1TraceConfig* cfg, const Go1TraceBuffers* buf, int32_t row, void* stream) {
+  if (!cfg || !buf || cfg->num_envs <= 0) return -1;
+  if (cfg->num_traced <= 0 || cfg->capacity <= 0 || !buf->trace) return -2;
+  if (!buf->base_lin_vel || !buf->base_ang_vel || !buf->commands || !buf->root_states || !buf->contact_forces ||
+      !buf->desired_contact_states || !buf->torques || !buf->dof_vel || !buf->dof_pos || !buf->reset_buf) return -3;
+  if (buf->measured_heights && cfg->num_height_points <= 0) return -4;
+  if (!buf->env_ids && cfg->num_traced != cfg->num_envs) return -8;
+  if (row < 0 || row >= cfg->capacity) return -7;
+  TraceArgs A; A.c = *cfg; A.b = *buf; A.row = row;
+  hipLaunchKernelGGL(trace_record_kernel, env_grid(cfg->num_traced), dim3(ACC_THREADS), 0, (hipStream_t)stream, A);
+  return hipGetLastError() == hipSuccess ? 0 : -20;
+}
+
+namespace {
+int check(const Go1ResponseConfig* cfg, const Go1ResponseBuffers* buf) {
+  if (!cfg || !buf || cfg->num_traced <= 0) return -1;
+  if (!buf->values || !buf->status) return -2;
+  if (cfg->num_signals < 1 || cfg->num_signals > GO1EVAL_MAX_SIGNALS) return -10;
+  return 0;
+}
+ResponseArgs args_of(const Go1ResponseConfig* cfg, const Go1ResponseBuffers* buf) { ResponseArgs A; A.c = *cfg; A.b = *buf; return A; }
+}  // namespace
+
+extern "C" int go1eval_response(const Go1ResponseConfig* cfg, const Go1ResponseBuffers* buf, void* stream) {
+  if (int rc = check(cfg, buf)) return rc;
+  if (!buf->trace) return -3;
+  const int w = cfg->smooth, s0 = cfg->switch_row, rows = cfg->rows;
+  if (!(1 <= w && w <= cfg->pre + 1 && cfg->pre <= s0 && s0 < rows && cfg->hold >= 1 && cfg->tail >= 1 && cfg->hold <= rows - s0 &&
+        cfg->tail <= rows - s0 && cfg->dt > 0.0f && cfg->band > 0.0f)) return -9;
+  for (int s = 0; s < cfg->num_signals; s++) {
+    const Go1ResponseSignal& g = cfg->signal[s];
+    if (g.y_channel < 0 || g.y_channel >= NT || g.r_channel >= NT) return -10;
+  }
+  const ResponseArgs A = args_of(cfg, buf);
+  hipLaunchKernelGGL(response_kernel, env_grid(cfg->num_traced), dim3(ACC_THREADS), 0, (hipStream_t)stream, A);
+  return hipGetLastError() == hipSuccess ? 0 : -20;
+}
+
+extern "C" int go1eval_response_reduce(const Go1ResponseConfig* cfg, const Go1ResponseBuffers* buf, void* stream) {
+  if (int rc = check(cfg, buf)) return rc;
+  if (cfg->num_groups <= 0 || !buf->group || !buf->results) return -5;
+  const ResponseArgs A = args_of(cfg, buf);
+  hipLaunchKernelGGL(response_reduce_kernel, dim3((unsigned)(cfg->num_groups * (cfg->num_signals * NR + 1))), dim3(RT), 0, (hipStream_t)stream, A);
   return hipGetLastError() == hipSuccess ? 0 : -20;
 }
 

@@ -149,6 +149,7 @@ class LeggedRobot(BaseTask):
         self._frames = [[], []]           # per camera: the last complete recording handed out
         self._metrics = None              # go1eval_host.Go1Eval, created by the first start_metrics()
         self._behaviour = None            # go1eval_host.Go1Behaviour, created by the first start_metrics(behaviour=True)
+        self._trace = None                # go1eval_host.Go1Trace, created by the first start_trace()
         if eval_cfg is not None:          # reference legged_robot.py:41-42
             self._parse_cfg(eval_cfg)
         self._parse_cfg(cfg)
@@ -443,6 +444,8 @@ class LeggedRobot(BaseTask):
             self._metrics.accumulate()
             if self._behaviour is not None and self._behaviour.armed:
                 self._behaviour.accumulate()
+        if self._trace is not None and self._trace.armed:
+            self._trace.record()
         if self._curriculum_sync and (self.common_step_counter + 1) % self.sim_config.curriculum_update_interval == 0:
             # ONE exchange for the last `curriculum_update_interval` steps' success counts (a slot per step), then the per-step
             # updates in order: every rank applies what a single process over the concatenated shards would
@@ -621,6 +624,39 @@ class LeggedRobot(BaseTask):
         if self._behaviour is not None and self._behaviour.table is not None:
             res["behaviour"] = self._behaviour.results()
         return res
+
+    # ---- the trace (include/go1eval.h, third kernel family): a per-step time series of 24 channels of chosen environments, written on
+    # the device by one more launch per step while it is armed, after the metrics launches; independent of start_metrics().  What the
+    # reference's scripts/play.py reads to the host after every step, and the step-response analysis of a command switch.
+    def start_trace(self, env_ids=None, capacity=None):
+        """begin a trace of the environments `env_ids` (None: all) with room for `capacity` steps (default: an episode,
+        max_episode_length + 2); steps beyond the capacity are not recorded"""
+        self._need_gpu_metrics("start_trace")
+        if self._trace is None:
+            import go1eval_host
+            self._trace = go1eval_host.Go1Trace(self.sim_config, self.buffers)
+        self._trace.arm(env_ids, int(self.max_episode_length) + 2 if capacity is None else capacity)
+
+    def stop_trace(self):
+        """stop recording; what was recorded stays readable"""
+        self._need_gpu_metrics("stop_trace")
+        if self._trace is not None:
+            self._trace.disarm()
+
+    def read_trace(self):
+        """{channel name: (rows, K) float32 array, "env_ids", "rows", "truncated"}: one device-to-host copy"""
+        self._need_gpu_metrics("read_trace")
+        if self._trace is None:
+            raise RuntimeError("read_trace(): start_trace() was never called")
+        return self._trace.read()
+
+    def trace_response(self, signals, switch_row, pre, smooth, band, hold, tail, groups, dt=None):
+        """the step response of the recorded trace around the command switch at row `switch_row` (go1eval_host.Go1Trace.response;
+        dt defaults to the policy step): two launches and one device-to-host copy"""
+        self._need_gpu_metrics("trace_response")
+        if self._trace is None:
+            raise RuntimeError("trace_response(): start_trace() was never called")
+        return self._trace.response(signals, switch_row, pre, smooth, band, hold, tail, self.dt if dt is None else dt, groups)
 
     def render(self, mode="rgb_array"):
         """reference :1612-1620: env 0 from its recording camera, now: (240, 360, 4) uint8 RGBA"""

@@ -2,7 +2,9 @@
 the per-environment accumulators and the result table of one simulator instance.
 
 Replaces calling the reference's go1_gym_learn/eval_metrics/metrics.py functions (each ends in `.cpu()`) after every step:
-`accumulate()` enqueues one launch and the host reads one small table when it asks for `results()`.
+`accumulate()` enqueues one launch and the host reads one small table when it asks for `results()`.  `Go1Behaviour` is the
+second table (gait and behaviour tracking); `Go1Trace` records a per-step time series of chosen environments on the device and
+analyses the step response to a command switch there (what the reference's scripts/play.py reads to the host step by step).
 """
 import ctypes
 import os
@@ -58,8 +60,45 @@ class Go1BehaviourBuffers(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in _BEHAVIOUR_INPUTS + _ACCUMULATORS + _STRIDE_STATE + ["group", "results"]]
 
 
+# ---- the trace and the step response (include/go1eval.h, third kernel family)
+TRACE_CHANNELS = ["lin_vel_x", "lin_vel_y", "ang_vel_yaw", "base_height", "contact_match", "power_consumption", "cmd_lin_vel_x",
+                  "cmd_lin_vel_y", "cmd_ang_vel_yaw", "cmd_base_height", "max_torques", "reset"] + [f"dof_pos_{j}" for j in range(12)]   # enum Go1TraceChannel
+RESPONSE_METRICS = ["reached", "rise_time", "overshoot", "settled", "settling_time", "steady_state_err", "iae"]       # enum Go1ResponseMetric
+RESPONSE_GROUP_FIELDS = ["envs", "ok", "reset", "not_held"]                                                          # enum Go1ResponseGroupField
+NUM_TRACE, NUM_RESPONSE, MAX_SIGNALS = 24, 7, 8
+
+
+class Go1TraceConfig(ctypes.Structure):
+    _fields_ = [("num_envs", ctypes.c_int32), ("num_traced", ctypes.c_int32), ("capacity", ctypes.c_int32),
+                ("num_height_points", ctypes.c_int32), ("base_height_target", ctypes.c_float)]
+
+
+_TRACE_INPUTS = ["base_lin_vel", "base_ang_vel", "commands", "root_states", "measured_heights", "contact_forces", "desired_contact_states",
+                 "torques", "dof_vel", "dof_pos", "reset_buf"]
+
+
+class Go1TraceBuffers(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in _TRACE_INPUTS + ["env_ids", "trace"]]
+
+
+class Go1ResponseSignal(ctypes.Structure):
+    _fields_ = [("y_channel", ctypes.c_int32), ("r_channel", ctypes.c_int32), ("fixed_target", ctypes.c_float), ("fixed_scale", ctypes.c_float)]
+
+
+class Go1ResponseConfig(ctypes.Structure):
+    _fields_ = [("num_traced", ctypes.c_int32), ("rows", ctypes.c_int32), ("switch_row", ctypes.c_int32), ("pre", ctypes.c_int32),
+                ("smooth", ctypes.c_int32), ("hold", ctypes.c_int32), ("tail", ctypes.c_int32), ("band", ctypes.c_float),
+                ("dt", ctypes.c_float), ("num_signals", ctypes.c_int32), ("num_groups", ctypes.c_int32),
+                ("signal", Go1ResponseSignal * MAX_SIGNALS)]
+
+
+class Go1ResponseBuffers(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ["trace", "values", "status", "group", "results"]]
+
+
 EXPORTED_SYMBOLS = ["go1eval_clear", "go1eval_accumulate", "go1eval_reduce", "go1eval_version",
-                    "go1eval_behaviour_clear", "go1eval_behaviour_accumulate", "go1eval_behaviour_reduce"]
+                    "go1eval_behaviour_clear", "go1eval_behaviour_accumulate", "go1eval_behaviour_reduce",
+                    "go1eval_trace_record", "go1eval_response", "go1eval_response_reduce"]
 
 _lib = None
 
@@ -86,6 +125,11 @@ def load_library(path=None):
     cfg_p, buf_p = ctypes.POINTER(Go1BehaviourConfig), ctypes.POINTER(Go1BehaviourBuffers)
     for fn in ("go1eval_behaviour_clear", "go1eval_behaviour_accumulate", "go1eval_behaviour_reduce"):
         getattr(lib, fn).argtypes = [cfg_p, buf_p, ctypes.c_void_p]
+        getattr(lib, fn).restype = ctypes.c_int
+    lib.go1eval_trace_record.argtypes = [ctypes.POINTER(Go1TraceConfig), ctypes.POINTER(Go1TraceBuffers), ctypes.c_int32, ctypes.c_void_p]
+    lib.go1eval_trace_record.restype = ctypes.c_int
+    for fn in ("go1eval_response", "go1eval_response_reduce"):
+        getattr(lib, fn).argtypes = [ctypes.POINTER(Go1ResponseConfig), ctypes.POINTER(Go1ResponseBuffers), ctypes.c_void_p]
         getattr(lib, fn).restype = ctypes.c_int
     lib.go1eval_version.restype = ctypes.c_char_p
     if path is None:
@@ -244,3 +288,118 @@ class Go1Behaviour:
         """{behaviour metric name: (G, 6) array with the columns FIELD_NAMES}: one launch and one device-to-host copy"""
         table = self.reduce().cpu().numpy()
         return {name: table[:, m, :].copy() for m, name in enumerate(BEHAVIOUR_NAMES)}
+
+
+def response_signals(cfg, signals):
+    """fill cfg.signal / cfg.num_signals from {name: (y_channel, r_channel or None[, fixed_target, fixed_scale])}; returns the names"""
+    names = list(signals)
+    if not 1 <= len(names) <= MAX_SIGNALS:
+        raise ValueError(f"response: between 1 and {MAX_SIGNALS} signals, not {len(names)}")
+    for s, name in enumerate(names):
+        y, r, target, scale = (tuple(signals[name]) + (0.0, 0.0))[:4]
+        g = cfg.signal[s]
+        g.y_channel, g.r_channel, g.fixed_target, g.fixed_scale = int(y), -1 if r is None else int(r), float(target), float(scale)
+    cfg.num_signals = len(names)
+    return names
+
+
+class Go1Trace:
+    """The trace of one simulator instance: a ring of `capacity` rows x 24 channels x K traced environments on the device, one
+    launch per recorded step, and the step-response analysis of what it holds.  S: the simulator's Go1SimConfig, buffers: its
+    SimBuffers (device tensors).  Nothing is allocated before the first arm()."""
+
+    def __init__(self, S, buffers, lib=None):
+        self.lib = lib if lib is not None else load_library()
+        self.buffers = buffers
+        self.device = buffers.device
+        c = self.cfg = Go1TraceConfig()
+        c.num_envs, c.base_height_target = int(S.num_envs), float(S.base_height_target)
+        self.measure_heights = bool(S.measure_heights)
+        c.num_height_points = int(buffers.measured_heights.shape[0]) if self.measure_heights else 0
+        self.buf = Go1TraceBuffers()
+        self.trace = self.ids = self.env_ids = None
+        self.rows, self.truncated, self.armed = 0, False, False
+
+    _stream, _check = Go1Eval._stream, Go1Eval._check
+
+    def arm(self, env_ids=None, capacity=1):
+        """start a trace of the environments `env_ids` (None: all of them, in order) with room for `capacity` steps"""
+        N = self.cfg.num_envs
+        if env_ids is None:
+            self.env_ids, self.ids = np.arange(N, dtype=np.int32), None
+        else:
+            ids = np.asarray(torch.as_tensor(env_ids).cpu(), dtype=np.int64).reshape(-1)            # (on the host, before the step loop)
+            if ids.size == 0 or ids.min() < 0 or ids.max() >= N:
+                raise ValueError(f"trace: environment ids have to lie in [0, {N})")
+            if np.unique(ids).size != ids.size:
+                raise ValueError("trace: an environment is named twice")
+            self.env_ids = ids.astype(np.int32)
+            self.ids = torch.from_numpy(self.env_ids).to(self.device)
+        K, capacity = int(self.env_ids.size), int(capacity)
+        if capacity < 1:
+            raise ValueError("trace: capacity has to be at least 1")
+        if self.trace is None or tuple(self.trace.shape) != (capacity, NUM_TRACE, K):
+            self.trace = torch.zeros(capacity, NUM_TRACE, K, dtype=torch.float32, device=self.device)
+        self.cfg.num_traced, self.cfg.capacity = K, capacity
+        b, B = self.buf, self.buffers
+        for n in _TRACE_INPUTS:
+            setattr(b, n, getattr(B, n).data_ptr())
+        if not self.measure_heights:
+            b.measured_heights = None
+        b.env_ids = self.ids.data_ptr() if self.ids is not None else None
+        b.trace = self.trace.data_ptr()
+        self.rows, self.truncated, self.armed = 0, False, True
+
+    def record(self):
+        """after a step: the next row (one launch, no sync).  A full ring records nothing more and sets `truncated`."""
+        if self.rows >= self.cfg.capacity:
+            self.truncated = True
+            return
+        self._check(self.lib.go1eval_trace_record(ctypes.byref(self.cfg), ctypes.byref(self.buf), self.rows, self._stream()), "go1eval_trace_record")
+        self.rows += 1
+
+    def disarm(self):
+        """stop recording (the trace keeps what it holds for `read()` and `response()`)"""
+        self.armed = False
+
+    def read(self):
+        """{channel name: (rows, K) float32 array} plus "env_ids" (K,), "rows" and "truncated": one device-to-host copy"""
+        assert self.trace is not None, "arm() first"
+        t = self.trace[:self.rows].cpu().numpy()
+        out = {name: t[:, c, :].copy() for c, name in enumerate(TRACE_CHANNELS)}
+        out.update(env_ids=self.env_ids.copy(), rows=self.rows, truncated=self.truncated)
+        return out
+
+    def response(self, signals, switch_row, pre, smooth, band, hold, tail, dt, groups):
+        """The step response of the recorded rows.  signals: {name: (y_channel, r_channel or None[, fixed_target, fixed_scale])};
+        groups: one int per traced environment (-1: not evaluated).  Returns {signal: {metric: (G, 6) array with the columns
+        FIELD_NAMES}}, "groups": (G, 4) array with the columns RESPONSE_GROUP_FIELDS, "values": {signal: {metric: (K,) float32}}
+        and "status": (K,) int32.  Two launches and one device-to-host copy."""
+        assert self.trace is not None, "arm() first"
+        K = int(self.cfg.num_traced)
+        c = Go1ResponseConfig()
+        names = response_signals(c, signals)
+        S = len(names)
+        g = torch.as_tensor(groups).to(torch.int32).reshape(-1)
+        assert g.numel() == K, (g.numel(), K)
+        G = int(g.max()) + 1
+        assert G >= 1, "no traced environment carries a group id >= 0"
+        c.num_traced, c.rows, c.switch_row, c.pre, c.smooth, c.hold, c.tail = K, self.rows, int(switch_row), int(pre), int(smooth), int(hold), int(tail)
+        c.band, c.dt, c.num_groups = float(band), float(dt), G
+        R = S * NUM_RESPONSE + 1
+        nbytes = [G * R * NUM_FIELDS * 8, S * NUM_RESPONSE * K * 4, K * 4]            # results (fp64 first: aligned), values, status
+        out = torch.zeros(sum(nbytes), dtype=torch.uint8, device=self.device)
+        group = g.to(self.device)
+        b = Go1ResponseBuffers()
+        b.trace, b.group = self.trace.data_ptr(), group.data_ptr()
+        b.results, b.values, b.status = out.data_ptr(), out.data_ptr() + nbytes[0], out.data_ptr() + nbytes[0] + nbytes[1]
+        self._check(self.lib.go1eval_response(ctypes.byref(c), ctypes.byref(b), self._stream()), "go1eval_response")
+        self._check(self.lib.go1eval_response_reduce(ctypes.byref(c), ctypes.byref(b), self._stream()), "go1eval_response_reduce")
+        host = out.cpu().numpy()
+        table = host[:nbytes[0]].view(np.float64).reshape(G, R, NUM_FIELDS)
+        values = host[nbytes[0]:nbytes[0] + nbytes[1]].view(np.float32).reshape(S, NUM_RESPONSE, K)
+        res = {name: {m: table[:, s * NUM_RESPONSE + i, :].copy() for i, m in enumerate(RESPONSE_METRICS)} for s, name in enumerate(names)}
+        res["groups"] = table[:, R - 1, :len(RESPONSE_GROUP_FIELDS)].copy()
+        res["values"] = {name: {m: values[s, i].copy() for i, m in enumerate(RESPONSE_METRICS)} for s, name in enumerate(names)}
+        res["status"] = host[nbytes[0] + nbytes[1]:].view(np.int32).copy()
+        return res
