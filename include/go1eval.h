@@ -171,6 +171,64 @@
  *   one value values[s][m][k] by the folding rule above: a non-finite value counts in nonfinite and enters nothing else; a finite
  *   value v has count 1, sum v, sumsq v * v (fp64), min = max = v.  The last row of a group: traced environments, environments
  *   with status 0, with status 1, with status 2, 0, 0 (sums in the same fixed order).
+ *
+ * ---- the push and the disturbance recovery (fourth kernel family) ----------------------------------------------------------------
+ * The response family measures what follows a change of the COMMAND.  This family changes the ROBOT: one launch adds a chosen
+ * velocity step to the base of chosen environments between two simulator steps, and the recovery analysis turns a trace that
+ * holds ONE such push under constant commands into fall, peak velocity error, recovery time, height drop, yaw-rate deviation and
+ * integrated excess error per environment, reduced per group by the tables' fixed-order reduction.  The trace is the third
+ * family's, its 24 channels unchanged.  (The reference's _push_robots draws a random planar velocity at a fixed episode
+ * interval and REPLACES the base velocity with it; nothing about it is chosen per environment and nothing is measured.)
+ *
+ * go1eval_push(cfg, buf, stream): one launch, one thread per pushed environment k in [0, K), K = num_pushed.  It pushes
+ *   environment env_ids[k]; env_ids == NULL means k itself and needs K == N (-8 otherwise, as go1eval_trace_record).  The four
+ *   values of k are push[r * K + k] for the rows r (index = Go1PushRow): forward, left, up velocity step (m/s) and yaw-rate step
+ *   (rad/s).  Forward and left are in the robot's HEADING FRAME (the world x-y plane turned by the robot's yaw); up and the yaw
+ *   rate are about world z.  Every operation is an fp32 operation; 1e-6 is an fp32 constant; q = root_states rows 3..6 (xyzw):
+ *     f = R(q) (1, 0, 0) by R(q) v = v + w t + u x t, u = q.xyz, t = 2 (u x v)      (the body's forward axis in the world)
+ *     n = sqrtf(f.x^2 + f.y^2);  heading h = (f.x / n, f.y / n), or (1, 0) when n < 1e-6   (a robot that points straight up or down)
+ *     row 7 += dv_forward * h.x - dv_left * h.y;   row 8 += dv_forward * h.y + dv_left * h.x;   row 9 += dv_up;   row 12 += dyaw
+ *   There is no trigonometry on the device: a push direction becomes its cosine and sine on the host.  An environment whose four
+ *   values all compare equal to zero is NOT WRITTEN (x + 0.0f turns -0.0f into +0.0f, and a zero push leaves every bit as it is).
+ *   An id outside [0, N) is skipped.  With env_ids == NULL a wavefront's loads and stores of one row are one contiguous run.  Every
+ *   element has one writer PROVIDED no id occurs twice; the kernel does not check that, nor that the table is finite: the host
+ *   wrapper (go1eval_host.Go1Push) refuses both before the launch.
+ *
+ * go1eval_recovery(cfg, buf, stream): one launch, one thread per traced environment, a pure function of the trace.  rows = the
+ *   recorded rows, p0 = push_row (the first row recorded AFTER the push: the state one simulator step after it), w = smooth,
+ *   end = rows.  Refused before the launch (-11) unless 1 <= pre <= p0, p0 < rows, 1 <= w <= pre + 1, 1 <= hold <= rows - p0,
+ *   dt > 0 and band >= 0.  band is an absolute velocity error in m/s.  c[t] below is channel c of this environment at row t; every
+ *   operation that is not marked fp64 is an fp32 operation on fp32 values.
+ *   1. Status (index = Go1RecoveryStatus), the first rule that applies:
+ *      1  some row in [p0 - pre, p0) has channel 11 != 0: the baseline is spoiled (a NaN, the trace of an id outside [0, N), is != 0)
+ *      3  some row in [p0, end) has channel 11 != 0: the robot fell (or timed out) after the push
+ *      2  channel 6, 7 or 8 has a row t in [p0 - pre, end) with c[t] != c[p0 - pre]: the command was not held
+ *      0  otherwise.
+ *      The fall is tested BEFORE the command: the row of a reset carries the reset's own command draw, so a fallen robot's commands
+ *      always moved as well.  Status 1 and 2: all eight values are NaN.  Status 3: fell = 1 and the other seven are NaN.
+ *   2. Signals per row t: e[t] = sqrtf(dx * dx + dy * dy) with dx = c0[t] - c6[t], dy = c1[t] - c7[t] (the planar velocity error);
+ *      z[t] = c3[t] (base height); y[t] = c2[t] - c8[t] (the yaw-rate error).  For x in {e, z, y}:
+ *      xs(t) = the mean of x over rows t - w + 1 .. t: added in an fp64 carry in ascending row order, divided by (double)w in fp64,
+ *              rounded to fp32 once (the response's box filter);
+ *      xb    = the mean of the RAW x over rows [p0 - pre, p0): the same carry, divided by (double)pre, rounded to fp32 once.
+ *   3. Eight values (index = Go1RecoveryMetric), t over [p0, end) in ascending order:
+ *      fell            0 (1 with status 3)
+ *      peak_vel_err    es(t_peak) - eb, t_peak = the FIRST t at which es(t) is largest (es(t) > every earlier es)
+ *      peak_time       (float)(t_peak - p0 + 1) * dt
+ *      recovered       t_s starts at p0 and becomes t + 1 whenever es(t) - eb > band; 1 if t_s <= end - hold, else 0
+ *      recovery_time   (float)(t_s - p0) * dt; NaN when not recovered; 0 when the signal never left the band
+ *      height_drop     zb - the fold of fminf over zs(t), starting from +inf
+ *      yaw_rate_dev    the fold of fmaxf over |ys(t) - yb|, starting from 0
+ *      iae_excess      dt * the sum of the RAW e[t] - eb: the fp32 differences added in an fp64 carry, multiplied by (double)dt in
+ *                      fp64, rounded to fp32 once.  Negative when the robot tracked better after the push than before it.
+ *      The box filter delays xs by about (w - 1) / 2 rows, and that delay is inside peak_time and recovery_time.  Roll and pitch
+ *      are no trace channel and are not measured; a fall is seen through the reset flag.
+ *   4. Outputs: values[m * K + k] (fp32) for value m, and status[k] (int32).  One writer each, no atomics.
+ *
+ * go1eval_recovery_reduce(cfg, buf, stream): results[num_groups][GO1EVAL_NUM_RECOVERY + 1][GO1EVAL_NUM_FIELDS] over the traced
+ *   environments with group[k] == g.  Row m is the metric row of go1eval_reduce over accumulators that folded the one value
+ *   values[m][k], exactly as go1eval_response_reduce forms its rows (a NaN counts in nonfinite).  The last row of a group
+ *   (index = Go1RecoveryGroupField): traced environments, environments with status 0, 1, 2, 3, then 0 (sums in the same fixed order).
  */
 #ifndef GO1EVAL_H_INCLUDED
 #define GO1EVAL_H_INCLUDED
@@ -387,6 +445,64 @@ int go1eval_response(const Go1ResponseConfig* cfg, const Go1ResponseBuffers* buf
 
 /* the response table from values and status (which it leaves as they are).  One launch. */
 int go1eval_response_reduce(const Go1ResponseConfig* cfg, const Go1ResponseBuffers* buf, void* stream);
+
+/* ---- the push and the disturbance recovery ------------------------------------------------------------------------------------ */
+#define GO1EVAL_NUM_PUSH 4
+#define GO1EVAL_NUM_RECOVERY 8
+
+/* rows of the push table */
+enum Go1PushRow { GO1PUSH_FORWARD = 0, GO1PUSH_LEFT = 1, GO1PUSH_UP = 2, GO1PUSH_YAW_RATE = 3 };
+enum Go1RecoveryMetric {
+  GO1RECOVERY_FELL = 0, GO1RECOVERY_PEAK_VEL_ERR = 1, GO1RECOVERY_PEAK_TIME = 2, GO1RECOVERY_RECOVERED = 3, GO1RECOVERY_RECOVERY_TIME = 4,
+  GO1RECOVERY_HEIGHT_DROP = 5, GO1RECOVERY_YAW_RATE_DEV = 6, GO1RECOVERY_IAE_EXCESS = 7
+};
+enum Go1RecoveryStatus { GO1RECOVERY_S_OK = 0, GO1RECOVERY_S_BASELINE_RESET = 1, GO1RECOVERY_S_NOT_HELD = 2, GO1RECOVERY_S_FELL = 3 };
+/* columns of a group's own row (row GO1EVAL_NUM_RECOVERY) of the recovery table */
+enum Go1RecoveryGroupField {
+  GO1RECOVERY_G_ENVS = 0, GO1RECOVERY_G_OK = 1, GO1RECOVERY_G_BASELINE_RESET = 2, GO1RECOVERY_G_NOT_HELD = 3, GO1RECOVERY_G_FELL = 4
+};
+
+typedef struct Go1PushConfig {
+  int32_t num_envs;            /* N of the simulator's SoA buffers */
+  int32_t num_pushed;          /* K: pushed environments (== num_envs when env_ids is NULL) */
+} Go1PushConfig;
+
+typedef struct Go1PushBuffers {
+  float* root_states;          /* [13][N]; rows 3..6 are read, rows 7, 8, 9 and 12 are read and written */
+  const int32_t* env_ids;      /* [K] or NULL (environment k itself); no id twice */
+  const float* push;           /* [GO1EVAL_NUM_PUSH][K], finite */
+} Go1PushBuffers;
+
+typedef struct Go1RecoveryConfig {
+  int32_t num_traced;          /* K of the trace */
+  int32_t rows;                /* recorded rows (<= the trace's capacity) */
+  int32_t push_row;            /* p0: the first row recorded after the push */
+  int32_t pre;                 /* rows before p0: the baseline, and what the status rules cover */
+  int32_t smooth;              /* w: rows of the box filter */
+  int32_t hold;                /* rows at the end that have to stay inside the band for `recovered` */
+  float band;                  /* the recovery band: m/s of velocity error above the baseline */
+  float dt;                    /* s, the policy step */
+  int32_t num_groups;          /* G of the result table (go1eval_recovery_reduce) */
+} Go1RecoveryConfig;
+
+typedef struct Go1RecoveryBuffers {
+  const float* trace;          /* [rows][GO1EVAL_NUM_TRACE][K] */
+  float* values;               /* [GO1EVAL_NUM_RECOVERY][K] */
+  int32_t* status;             /* [K] */
+  /* go1eval_recovery_reduce */
+  const int32_t* group;        /* [K] */
+  double* results;             /* [num_groups][GO1EVAL_NUM_RECOVERY + 1][GO1EVAL_NUM_FIELDS] */
+} Go1RecoveryBuffers;
+
+/* between two simulator steps: add the table's velocity steps to the base of the pushed environments.  One launch, one thread per
+ * pushed environment.  No root_states or no table, or num_pushed <= 0: -2.  env_ids == NULL with num_pushed != num_envs: -8. */
+int go1eval_push(const Go1PushConfig* cfg, const Go1PushBuffers* buf, void* stream);
+
+/* the recovery of every traced environment from the trace.  One launch.  No outputs: -2; no trace: -3; window refused: -11. */
+int go1eval_recovery(const Go1RecoveryConfig* cfg, const Go1RecoveryBuffers* buf, void* stream);
+
+/* the recovery table from values and status (which it leaves as they are).  One launch.  No group, no table or no groups: -5. */
+int go1eval_recovery_reduce(const Go1RecoveryConfig* cfg, const Go1RecoveryBuffers* buf, void* stream);
 
 /* "go1eval <version> (gfx950) go1-src:<16 hex digits of the source hash>" */
 const char* go1eval_version(void);

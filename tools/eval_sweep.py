@@ -20,6 +20,14 @@ values (NAME: a name of COMMAND_INDEX, or `gait` with gait names); the trace aro
 device (go1_gym_learn.eval_metrics.response), `<out>/eval/<preset>_response.json` is written and the step-response table is
 printed and appended to `<out>/eval/<preset>_response.md`.  `--trace-envs I [I ...]` also writes those environments' traces to
 `<out>/eval/<preset>_trace.npz` and the velocity / joint-position figure of each to `<preset>_trace_env<I>.png`.
+
+    python tools/eval_sweep.py --checkpoint RUN_DIR/checkpoints --out RUN_DIR --push --magnitude 0 0.5 1.0 --direction 0 90 180 270
+
+With `--push` every environment trots at 1 m/s and is pushed once with one cell of the `--magnitude M ...` (m/s) x `--direction D ...`
+(degrees in the robot's heading frame: 0 a shove from behind, 90 a push to the left) grid; the trace around the push is recorded
+and analysed on the device (go1_gym_learn.eval_metrics.recovery), `<out>/eval/<preset>_push.json` is written and the recovery table
+is printed and appended to `<out>/eval/<preset>_push.md`.  `--trace-envs I [I ...]` also writes `<preset>_push_trace.npz` and the
+figure of each to `<preset>_push_trace_env<I>.png`.
 Run on the GPU box."""
 import argparse
 import json
@@ -94,11 +102,25 @@ def parse_args(argv=None):
     ap.add_argument("--axis", nargs="+", action="append", metavar=("NAME", "VALUE"), help="a behaviour command and its values; repeatable")
     ap.add_argument("--response", action="store_true", help="measure the step response to the --switch of one command instead of the velocity grid")
     ap.add_argument("--switch", nargs="+", metavar=("NAME", "VALUE"), help="the switched command, its value before and its values after")
-    ap.add_argument("--trace-envs", nargs="+", type=int, default=None, help="with --response: environments whose trace and figure are written")
+    ap.add_argument("--trace-envs", nargs="+", type=int, default=None, help="with --response or --push: environments whose trace and figure are written")
+    ap.add_argument("--push", action="store_true", help="measure the recovery from one push per environment over the --magnitude x --direction grid")
+    ap.add_argument("--magnitude", nargs="+", type=float, default=None, help="with --push: velocity steps in m/s; 0 is the control cell")
+    ap.add_argument("--direction", nargs="+", type=float, default=None,
+                    help="with --push: directions in degrees in the robot's heading frame (0 a shove from behind, 90 a push to the left)")
     ap.add_argument("--out", required=True)
     a = ap.parse_args(argv)
-    if (a.switch or a.trace_envs) and not a.response:
-        ap.error("--switch and --trace-envs need --response")
+    if a.switch and not a.response:
+        ap.error("--switch needs --response")
+    if a.trace_envs and not (a.response or a.push):
+        ap.error("--trace-envs needs --response or --push")
+    if (a.magnitude or a.direction) and not a.push:
+        ap.error("--magnitude and --direction need --push")
+    if a.push and (a.response or a.behaviour):
+        ap.error("--push excludes --response and --behaviour")
+    if a.push and not (a.magnitude and a.direction):
+        ap.error("--push needs --magnitude M [M ...] and --direction D [D ...]")
+    if a.push and any(m < 0 for m in a.magnitude):
+        ap.error("--magnitude: a push has no negative magnitude; turn its direction by 180 degrees")
     if a.response and (not a.switch or len(a.switch) < 3):
         ap.error("--response needs --switch NAME FROM TO [TO ...]")
     return a
@@ -133,6 +155,26 @@ def run_response(a, policy):
                 response.plot_trace(res["trace"], e, f"{stem}_trace_env{e}.png", dt=res["dt"])
 
 
+def run_push(a, policy):
+    import numpy as np
+    from go1_gym_learn.eval_metrics import recovery, response
+    for preset in a.presets:
+        res = recovery.run_push_sweep(policy, preset, a.magnitude, a.direction, num_envs=a.envs, seed=a.seed, terrain=a.terrain,
+                                      trace_envs=a.trace_envs)
+        stem = os.path.join(a.out, "eval", preset)
+        with open(stem + "_push.json", "w") as f:
+            json.dump(recovery.recovery_to_json(res), f, indent=1)
+        text = f"### {preset}: {a.envs} environments, pushes of {a.magnitude} m/s towards {a.direction} degrees, recovery\n\n"
+        text += recovery.recovery_markdown_table(res) + "\n"
+        print(text)
+        with open(stem + "_push.md", "a") as f:
+            f.write(text + "\n")
+        if a.trace_envs:
+            np.savez(stem + "_push_trace.npz", **res["trace"])
+            for e in a.trace_envs:
+                response.plot_trace(res["trace"], e, f"{stem}_push_trace_env{e}.png", dt=res["dt"])
+
+
 def behaviour_axes(a):
     """{command name: [values]} of the --axis options, in the order given"""
     from go1_gym_learn.eval_metrics.behaviour import COMMAND_INDEX
@@ -155,6 +197,8 @@ def main(argv=None):
     os.makedirs(os.path.join(a.out, "eval"), exist_ok=True)
     if a.response:
         return run_response(a, policy)
+    if a.push:
+        return run_push(a, policy)
     if a.behaviour:
         from go1_gym_learn.eval_metrics import behaviour
         axes = behaviour_axes(a)

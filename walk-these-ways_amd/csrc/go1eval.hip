@@ -12,6 +12,9 @@
 // trace_record_kernel / response_kernel / response_reduce_kernel: the trace and the step response, the same shapes again: one
 // thread per traced environment; a channel of a trace row is [K] consecutive floats, so both the stores of the record and the
 // loads of the analysis (sequential over the rows per thread) are contiguous across a wavefront.  tests/response_ref.py is the model.
+// push_kernel / recovery_kernel / recovery_reduce_kernel: the push and the disturbance recovery: one thread per pushed environment
+// that adds a velocity step to its rows of root_states, and the response's shapes for the analysis of the trace that follows
+// (the same loads, the same reduction through reduce_metric_row and status_row).  tests/recovery_ref.py is the model.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -422,12 +425,34 @@ struct FoldedOnce {
   const int32_t* group;
   Count count; Nonfinite nonfinite; Sum sum; Sumsq sumsq; Value min, max;
 };
+
+// the last row of a group of the response and recovery tables, by one workgroup of RT threads in reduce_metric_row's combination
+// order: traced environments, environments with status 0, 1, 2, 3, then 0 (the response knows no status 3: its count is 0)
+__device__ __forceinline__ void status_row(const int32_t* status, const int32_t* group, int g, int K, double (*lds)[RT], double* out) {
+  const int t = (int)threadIdx.x;
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = 0.0;
+  for (int e = t; e < K; e += RT) {
+    if (group[e] != g) continue;
+    const int st = status[e];
+    a0 += 1.0; a1 += st == 0 ? 1.0 : 0.0; a2 += st == 1 ? 1.0 : 0.0; a3 += st == 2 ? 1.0 : 0.0; a4 += st == 3 ? 1.0 : 0.0;
+  }
+  lds[0][t] = a0; lds[1][t] = a1; lds[2][t] = a2; lds[3][t] = a3; lds[4][t] = a4;
+  __syncthreads();
+  for (int s = RT / 2; s > 0; s >>= 1) {
+    if (t < s) {
+      for (int f = 0; f < 5; f++) lds[f][t] += lds[f][t + s];
+    }
+    __syncthreads();
+  }
+  if (t != 0) return;
+  for (int f = 0; f < 5; f++) out[f] = lds[f][0];
+  out[5] = 0.0;
+}
 }  // namespace
 
 extern "C" __global__ void __launch_bounds__(RT) response_reduce_kernel(const ResponseArgs A) {
   __shared__ double lds[NF][RT];
   const int K = A.c.num_traced, rows = A.c.num_signals * NR + 1;
-  const int t = (int)threadIdx.x;
   const int g = (int)blockIdx.x / rows, m = (int)blockIdx.x % rows;
   const Go1ResponseBuffers& b = A.b;
   double* out = b.results + ((size_t)g * rows + m) * NF;
@@ -437,24 +462,118 @@ extern "C" __global__ void __launch_bounds__(RT) response_reduce_kernel(const Re
     reduce_metric_row(once, g, m, K, lds, out);
     return;
   }
-  // the group's own row: a0 traced environments, a1 status 0, a2 status 1, a3 status 2
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-  for (int e = t; e < K; e += RT) {
-    if (b.group[e] != g) continue;
-    const int st = b.status[e];
-    a0 += 1.0; a1 += st == 0 ? 1.0 : 0.0; a2 += st == 1 ? 1.0 : 0.0; a3 += st == 2 ? 1.0 : 0.0;
-  }
-  lds[0][t] = a0; lds[1][t] = a1; lds[2][t] = a2; lds[3][t] = a3;
-  __syncthreads();
-  for (int s = RT / 2; s > 0; s >>= 1) {
-    if (t < s) {
-      for (int f = 0; f < 4; f++) lds[f][t] += lds[f][t + s];
+  status_row(b.status, b.group, g, K, lds, out);
+}
+
+// ---- the push and the disturbance recovery --------------------------------------------------------------------------------------
+constexpr int NV = GO1EVAL_NUM_RECOVERY;
+
+struct PushArgs {
+  Go1PushConfig c;
+  Go1PushBuffers b;
+};
+
+struct RecoveryArgs {
+  Go1RecoveryConfig c;
+  Go1RecoveryBuffers b;
+};
+
+extern "C" __global__ void __launch_bounds__(ACC_THREADS) push_kernel(const PushArgs A) {
+  const int N = A.c.num_envs, K = A.c.num_pushed;
+  const int k = (int)(blockIdx.x * ACC_THREADS + threadIdx.x);
+  if (k >= K) return;
+  const Go1PushBuffers& b = A.b;
+  const float forward = b.push[(size_t)GO1PUSH_FORWARD * K + k], left = b.push[(size_t)GO1PUSH_LEFT * K + k];     // consecutive k, consecutive floats
+  const float up = b.push[(size_t)GO1PUSH_UP * K + k], dyaw = b.push[(size_t)GO1PUSH_YAW_RATE * K + k];
+  if (forward == 0.0f && left == 0.0f && up == 0.0f && dyaw == 0.0f) return;       // a zero push writes nothing: -0.0f stays -0.0f
+  const int e = b.env_ids ? b.env_ids[k] : k;
+  if (e < 0 || e >= N) return;
+  float* root = b.root_states + e;                                                 // row r at root[r * N]
+  const V3 f = quat_rotate(root[(size_t)3 * N], root[(size_t)4 * N], root[(size_t)5 * N], root[(size_t)6 * N], V3{1.0f, 0.0f, 0.0f});
+  const float n = sqrtf(f.x * f.x + f.y * f.y);
+  float hx = 1.0f, hy = 0.0f;
+  if (!(n < 1e-6f)) { hx = f.x / n; hy = f.y / n; }
+  root[(size_t)7 * N] += forward * hx - left * hy;
+  root[(size_t)8 * N] += forward * hy + left * hx;
+  root[(size_t)9 * N] += up;
+  root[(size_t)12 * N] += dyaw;
+}
+
+extern "C" __global__ void __launch_bounds__(ACC_THREADS) recovery_kernel(const RecoveryArgs A) {
+  const Go1RecoveryConfig& c = A.c;
+  const int K = c.num_traced;
+  const int k = (int)(blockIdx.x * ACC_THREADS + threadIdx.x);
+  if (k >= K) return;
+  const float* trace = A.b.trace;
+  const auto at = [trace, K, k](int t, int ch) { return trace[((size_t)t * NT + ch) * K + k]; };   // consecutive k, consecutive floats
+  const int p0 = c.push_row, first = c.push_row - c.pre, end = c.rows, w = c.smooth;
+
+  bool spoiled = false, fell = false, moved = false;
+  for (int t = first; t < end; t++) {
+    if (at(t, GO1TRACE_RESET) != 0.0f) { if (t < p0) spoiled = true; else fell = true; }
+    for (int ch = GO1TRACE_CMD_LIN_VEL_X; ch <= GO1TRACE_CMD_ANG_VEL_YAW; ch++) {
+      if (at(t, ch) != at(first, ch)) moved = true;
     }
-    __syncthreads();
   }
-  if (t != 0) return;
-  out[GO1RESPONSE_G_ENVS] = lds[0][0]; out[GO1RESPONSE_G_OK] = lds[1][0]; out[GO1RESPONSE_G_RESET] = lds[2][0];
-  out[GO1RESPONSE_G_NOT_HELD] = lds[3][0]; out[4] = 0.0; out[5] = 0.0;
+  const int status = spoiled ? GO1RECOVERY_S_BASELINE_RESET : fell ? GO1RECOVERY_S_FELL : moved ? GO1RECOVERY_S_NOT_HELD : GO1RECOVERY_S_OK;
+  A.b.status[k] = status;
+  float* out = A.b.values + k;
+  if (status != GO1RECOVERY_S_OK) {
+    for (int m = 0; m < NV; m++) out[(size_t)m * K] = NAN;
+    if (status == GO1RECOVERY_S_FELL) out[(size_t)GO1RECOVERY_FELL * K] = 1.0f;
+    return;
+  }
+
+  // the three signals of a row: planar velocity error, base height, yaw-rate error
+  const auto vel_err = [&at](int t) {
+    const float dx = at(t, GO1TRACE_LIN_VEL_X) - at(t, GO1TRACE_CMD_LIN_VEL_X), dy = at(t, GO1TRACE_LIN_VEL_Y) - at(t, GO1TRACE_CMD_LIN_VEL_Y);
+    return sqrtf(dx * dx + dy * dy);
+  };
+  const auto height = [&at](int t) { return at(t, GO1TRACE_BASE_HEIGHT); };
+  const auto yaw_err = [&at](int t) { return at(t, GO1TRACE_ANG_VEL_YAW) - at(t, GO1TRACE_CMD_ANG_VEL_YAW); };
+  // the mean over rows [from, to): fp64 carry in ascending order, rounded once
+  const auto mean = [](const auto& x, int from, int to) {
+    double sum = 0.0;
+    for (int u = from; u < to; u++) sum += (double)x(u);
+    return (float)(sum / (double)(to - from));
+  };
+  const float eb = mean(vel_err, first, p0), zb = mean(height, first, p0), yb = mean(yaw_err, first, p0);
+
+  int t_peak = p0, t_s = p0;
+  float peak = -INFINITY, lowest = INFINITY, yaw_dev = 0.0f;
+  double excess = 0.0;
+  for (int t = p0; t < end; t++) {
+    const float es = mean(vel_err, t - w + 1, t + 1);
+    if (es > peak) { peak = es; t_peak = t; }
+    if (es - eb > c.band) t_s = t + 1;
+    lowest = fminf(lowest, mean(height, t - w + 1, t + 1));
+    yaw_dev = fmaxf(yaw_dev, fabsf(mean(yaw_err, t - w + 1, t + 1) - yb));
+    excess += (double)(vel_err(t) - eb);
+  }
+  const bool recovered = t_s <= end - c.hold;
+  out[(size_t)GO1RECOVERY_FELL * K] = 0.0f;
+  out[(size_t)GO1RECOVERY_PEAK_VEL_ERR * K] = peak - eb;
+  out[(size_t)GO1RECOVERY_PEAK_TIME * K] = (float)(t_peak - p0 + 1) * c.dt;
+  out[(size_t)GO1RECOVERY_RECOVERED * K] = recovered ? 1.0f : 0.0f;
+  out[(size_t)GO1RECOVERY_RECOVERY_TIME * K] = recovered ? (float)(t_s - p0) * c.dt : NAN;
+  out[(size_t)GO1RECOVERY_HEIGHT_DROP * K] = zb - lowest;
+  out[(size_t)GO1RECOVERY_YAW_RATE_DEV * K] = yaw_dev;
+  out[(size_t)GO1RECOVERY_IAE_EXCESS * K] = (float)((double)c.dt * excess);
+}
+
+extern "C" __global__ void __launch_bounds__(RT) recovery_reduce_kernel(const RecoveryArgs A) {
+  __shared__ double lds[NF][RT];
+  const int K = A.c.num_traced;
+  const int g = (int)blockIdx.x / (NV + 1), m = (int)blockIdx.x % (NV + 1);
+  const Go1RecoveryBuffers& b = A.b;
+  double* out = b.results + ((size_t)g * (NV + 1) + m) * NF;
+  if (m != NV) {
+    const float* v = b.values;
+    const FoldedOnce once = {b.group, {v}, {v}, {v}, {v}, {v}, {v}};
+    reduce_metric_row(once, g, m, K, lds, out);
+    return;
+  }
+  status_row(b.status, b.group, g, K, lds, out);
 }
 
 namespace {
@@ -573,6 +692,43 @@ extern "C" int go1eval_response_reduce(const Go1ResponseConfig* cfg, const Go1Re
   if (cfg->num_groups <= 0 || !buf->group || !buf->results) return -5;
   const ResponseArgs A = args_of(cfg, buf);
   hipLaunchKernelGGL(response_reduce_kernel, dim3((unsigned)(cfg->num_groups * (cfg->num_signals * NR + 1))), dim3(RT), 0, (hipStream_t)stream, A);
+  return hipGetLastError() == hipSuccess ? 0 : -20;
+}
+
+extern "C" int go1eval_push(const Go1PushConfig* cfg, const Go1PushBuffers* buf, void* stream) {
+  if (!cfg || !buf || cfg->num_envs <= 0) return -1;
+  if (cfg->num_pushed <= 0 || !buf->root_states || !buf->push) return -2;
+  if (!buf->env_ids && cfg->num_pushed != cfg->num_envs) return -8;
+  PushArgs A; A.c = *cfg; A.b = *buf;
+  hipLaunchKernelGGL(push_kernel, env_grid(cfg->num_pushed), dim3(ACC_THREADS), 0, (hipStream_t)stream, A);
+  return hipGetLastError() == hipSuccess ? 0 : -20;
+}
+
+namespace {
+int check(const Go1RecoveryConfig* cfg, const Go1RecoveryBuffers* buf) {
+  if (!cfg || !buf || cfg->num_traced <= 0) return -1;
+  if (!buf->values || !buf->status) return -2;
+  return 0;
+}
+RecoveryArgs args_of(const Go1RecoveryConfig* cfg, const Go1RecoveryBuffers* buf) { RecoveryArgs A; A.c = *cfg; A.b = *buf; return A; }
+}  // namespace
+
+extern "C" int go1eval_recovery(const Go1RecoveryConfig* cfg, const Go1RecoveryBuffers* buf, void* stream) {
+  if (int rc = check(cfg, buf)) return rc;
+  if (!buf->trace) return -3;
+  const int w = cfg->smooth, p0 = cfg->push_row, rows = cfg->rows;
+  if (!(1 <= cfg->pre && cfg->pre <= p0 && p0 < rows && 1 <= w && w <= cfg->pre + 1 && 1 <= cfg->hold && cfg->hold <= rows - p0 &&
+        cfg->dt > 0.0f && cfg->band >= 0.0f)) return -11;
+  const RecoveryArgs A = args_of(cfg, buf);
+  hipLaunchKernelGGL(recovery_kernel, env_grid(cfg->num_traced), dim3(ACC_THREADS), 0, (hipStream_t)stream, A);
+  return hipGetLastError() == hipSuccess ? 0 : -20;
+}
+
+extern "C" int go1eval_recovery_reduce(const Go1RecoveryConfig* cfg, const Go1RecoveryBuffers* buf, void* stream) {
+  if (int rc = check(cfg, buf)) return rc;
+  if (cfg->num_groups <= 0 || !buf->group || !buf->results) return -5;
+  const RecoveryArgs A = args_of(cfg, buf);
+  hipLaunchKernelGGL(recovery_reduce_kernel, dim3((unsigned)(cfg->num_groups * (NV + 1))), dim3(RT), 0, (hipStream_t)stream, A);
   return hipGetLastError() == hipSuccess ? 0 : -20;
 }
 

@@ -150,6 +150,7 @@ class LeggedRobot(BaseTask):
         self._metrics = None              # go1eval_host.Go1Eval, created by the first start_metrics()
         self._behaviour = None            # go1eval_host.Go1Behaviour, created by the first start_metrics(behaviour=True)
         self._trace = None                # go1eval_host.Go1Trace, created by the first start_trace()
+        self._push = None                 # go1eval_host.Go1Push, created by the first push_robots()
         if eval_cfg is not None:          # reference legged_robot.py:41-42
             self._parse_cfg(eval_cfg)
         self._parse_cfg(cfg)
@@ -657,6 +658,27 @@ class LeggedRobot(BaseTask):
         if self._trace is None:
             raise RuntimeError("trace_response(): start_trace() was never called")
         return self._trace.response(signals, switch_row, pre, smooth, band, hold, tail, self.dt if dt is None else dt, groups)
+
+    # ---- the push and the recovery from it (include/go1eval.h, fourth kernel family).  The reference's _push_robots draws a random
+    # planar velocity at a fixed interval and REPLACES the base velocity; this one ADDS a chosen velocity step to chosen environments.
+    def push_robots(self, push, env_ids=None):
+        """add a velocity step to the base of the environments `env_ids` (None: all, in order) now, between two step() calls:
+        push (K, 4) array or tensor of forward, left (the robot's heading frame), up (m/s) and yaw rate (rad/s) steps.  One launch
+        on the simulator's stream; the table is checked on the host first (finite, no id twice, ids in range)."""
+        self._need_gpu_metrics("push_robots")
+        if self._push is None:
+            import go1eval_host
+            self._push = go1eval_host.Go1Push(self.sim_config, self.buffers)
+        self._push.load(push, env_ids)
+        self._push.launch()
+
+    def trace_recovery(self, push_row, pre, smooth, band, hold, groups, dt=None):
+        """the recovery of the recorded trace from the push before row `push_row` (go1eval_host.Go1Trace.recovery; dt defaults to
+        the policy step): two launches and one device-to-host copy"""
+        self._need_gpu_metrics("trace_recovery")
+        if self._trace is None:
+            raise RuntimeError("trace_recovery(): start_trace() was never called")
+        return self._trace.recovery(push_row, pre, smooth, band, hold, self.dt if dt is None else dt, groups)
 
     def render(self, mode="rgb_array"):
         """reference :1612-1620: env 0 from its recording camera, now: (240, 360, 4) uint8 RGBA"""

@@ -1,4 +1,5 @@
 """Evaluation of trained policies: the reference's metric functions and domain-randomisation presets under their own names
 (`metrics.METRICS_FNS`, `domain_randomization.DR_SETTINGS`), and `sweep.run_sweep`, which measures the ten scalar metrics on
 the device (include/go1eval.h) over a grid of commands.  `behaviour` adds the second table: gait and behaviour tracking
-(`BEHAVIOUR_FNS`, `StrideTracker`, `run_behaviour_sweep`) over a product of the other commands' values."""
+(`BEHAVIOUR_FNS`, `StrideTracker`, `run_behaviour_sweep`) over a product of the other commands' values.  `response` measures the
+step response to a command switch from a trace recorded on the device, `recovery` the recovery from a push (`run_push_sweep`)."""

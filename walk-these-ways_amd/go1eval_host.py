@@ -5,6 +5,8 @@ Replaces calling the reference's go1_gym_learn/eval_metrics/metrics.py functions
 `accumulate()` enqueues one launch and the host reads one small table when it asks for `results()`.  `Go1Behaviour` is the
 second table (gait and behaviour tracking); `Go1Trace` records a per-step time series of chosen environments on the device and
 analyses the step response to a command switch there (what the reference's scripts/play.py reads to the host step by step).
+`Go1Push` adds a chosen velocity step to the base of chosen environments with one launch, and `Go1Trace.recovery` analyses the
+trace that follows it (fall, peak velocity error, recovery time, ...).
 """
 import ctypes
 import os
@@ -96,9 +98,36 @@ class Go1ResponseBuffers(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ["trace", "values", "status", "group", "results"]]
 
 
+# ---- the push and the disturbance recovery (include/go1eval.h, fourth kernel family)
+PUSH_ROWS = ["forward", "left", "up", "yaw_rate"]                                                                    # enum Go1PushRow
+RECOVERY_METRICS = ["fell", "peak_vel_err", "peak_time", "recovered", "recovery_time", "height_drop", "yaw_rate_dev", "iae_excess"]   # enum Go1RecoveryMetric
+RECOVERY_STATUS = ["ok", "baseline_reset", "not_held", "fell"]                                                       # enum Go1RecoveryStatus
+RECOVERY_GROUP_FIELDS = ["envs", "ok", "baseline_reset", "not_held", "fell"]                                         # enum Go1RecoveryGroupField
+NUM_PUSH, NUM_RECOVERY = 4, 8
+
+
+class Go1PushConfig(ctypes.Structure):
+    _fields_ = [("num_envs", ctypes.c_int32), ("num_pushed", ctypes.c_int32)]
+
+
+class Go1PushBuffers(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ["root_states", "env_ids", "push"]]
+
+
+class Go1RecoveryConfig(ctypes.Structure):
+    _fields_ = [("num_traced", ctypes.c_int32), ("rows", ctypes.c_int32), ("push_row", ctypes.c_int32), ("pre", ctypes.c_int32),
+                ("smooth", ctypes.c_int32), ("hold", ctypes.c_int32), ("band", ctypes.c_float), ("dt", ctypes.c_float),
+                ("num_groups", ctypes.c_int32)]
+
+
+class Go1RecoveryBuffers(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ["trace", "values", "status", "group", "results"]]
+
+
 EXPORTED_SYMBOLS = ["go1eval_clear", "go1eval_accumulate", "go1eval_reduce", "go1eval_version",
                     "go1eval_behaviour_clear", "go1eval_behaviour_accumulate", "go1eval_behaviour_reduce",
-                    "go1eval_trace_record", "go1eval_response", "go1eval_response_reduce"]
+                    "go1eval_trace_record", "go1eval_response", "go1eval_response_reduce",
+                    "go1eval_push", "go1eval_recovery", "go1eval_recovery_reduce"]
 
 _lib = None
 
@@ -130,6 +159,11 @@ def load_library(path=None):
     lib.go1eval_trace_record.restype = ctypes.c_int
     for fn in ("go1eval_response", "go1eval_response_reduce"):
         getattr(lib, fn).argtypes = [ctypes.POINTER(Go1ResponseConfig), ctypes.POINTER(Go1ResponseBuffers), ctypes.c_void_p]
+        getattr(lib, fn).restype = ctypes.c_int
+    lib.go1eval_push.argtypes = [ctypes.POINTER(Go1PushConfig), ctypes.POINTER(Go1PushBuffers), ctypes.c_void_p]
+    lib.go1eval_push.restype = ctypes.c_int
+    for fn in ("go1eval_recovery", "go1eval_recovery_reduce"):
+        getattr(lib, fn).argtypes = [ctypes.POINTER(Go1RecoveryConfig), ctypes.POINTER(Go1RecoveryBuffers), ctypes.c_void_p]
         getattr(lib, fn).restype = ctypes.c_int
     lib.go1eval_version.restype = ctypes.c_char_p
     if path is None:
@@ -403,3 +437,90 @@ class Go1Trace:
         res["values"] = {name: {m: values[s, i].copy() for i, m in enumerate(RESPONSE_METRICS)} for s, name in enumerate(names)}
         res["status"] = host[nbytes[0] + nbytes[1]:].view(np.int32).copy()
         return res
+
+    def recovery(self, push_row, pre, smooth, band, hold, dt, groups):
+        """The recovery from a push of the recorded rows: push_row = the first row recorded after the push, `pre` baseline rows
+        before it, a box filter of `smooth` rows, `band` in m/s above the baseline, `hold` rows at the end inside the band.
+        groups: one int per traced environment (-1: not evaluated).  Returns {metric: (G, 6) array with the columns FIELD_NAMES},
+        "groups": (G, 5) array with the columns RECOVERY_GROUP_FIELDS, "values": {metric: (K,) float32} and "status": (K,) int32
+        (RECOVERY_STATUS).  Two launches and one device-to-host copy."""
+        assert self.trace is not None, "arm() first"
+        K = int(self.cfg.num_traced)
+        g = torch.as_tensor(groups).to(torch.int32).reshape(-1)
+        assert g.numel() == K, (g.numel(), K)
+        G = int(g.max()) + 1
+        assert G >= 1, "no traced environment carries a group id >= 0"
+        c = Go1RecoveryConfig()
+        c.num_traced, c.rows, c.push_row, c.pre, c.smooth, c.hold = K, self.rows, int(push_row), int(pre), int(smooth), int(hold)
+        c.band, c.dt, c.num_groups = float(band), float(dt), G
+        R = NUM_RECOVERY + 1
+        nbytes = [G * R * NUM_FIELDS * 8, NUM_RECOVERY * K * 4, K * 4]                # results (fp64 first: aligned), values, status
+        out = torch.zeros(sum(nbytes), dtype=torch.uint8, device=self.device)
+        group = g.to(self.device)
+        b = Go1RecoveryBuffers()
+        b.trace, b.group = self.trace.data_ptr(), group.data_ptr()
+        b.results, b.values, b.status = out.data_ptr(), out.data_ptr() + nbytes[0], out.data_ptr() + nbytes[0] + nbytes[1]
+        self._check(self.lib.go1eval_recovery(ctypes.byref(c), ctypes.byref(b), self._stream()), "go1eval_recovery")
+        self._check(self.lib.go1eval_recovery_reduce(ctypes.byref(c), ctypes.byref(b), self._stream()), "go1eval_recovery_reduce")
+        host = out.cpu().numpy()
+        table = host[:nbytes[0]].view(np.float64).reshape(G, R, NUM_FIELDS)
+        values = host[nbytes[0]:nbytes[0] + nbytes[1]].view(np.float32).reshape(NUM_RECOVERY, K)
+        res = {m: table[:, i, :].copy() for i, m in enumerate(RECOVERY_METRICS)}
+        res["groups"] = table[:, R - 1, :len(RECOVERY_GROUP_FIELDS)].copy()
+        res["values"] = {m: values[i].copy() for i, m in enumerate(RECOVERY_METRICS)}
+        res["status"] = host[nbytes[0] + nbytes[1]:].view(np.int32).copy()
+        return res
+
+
+class Go1Push:
+    """Pushes of one simulator instance: a table of velocity steps (forward, left, up, yaw rate; PUSH_ROWS) for chosen environments,
+    checked on the host, held on the device, and added to the base velocities in root_states by one launch per `launch()`.
+    S: the simulator's Go1SimConfig, buffers: its SimBuffers (device tensors).  Nothing is allocated before the first load()."""
+
+    def __init__(self, S, buffers, lib=None):
+        self.lib = lib if lib is not None else load_library()
+        self.buffers = buffers
+        self.device = buffers.device
+        self.cfg = Go1PushConfig()
+        self.cfg.num_envs = int(S.num_envs)
+        self.buf = Go1PushBuffers()
+        self.table = self.ids = self.env_ids = None
+
+    _stream, _check = Go1Eval._stream, Go1Eval._check
+
+    def load(self, push, env_ids=None):
+        """the table of the next launches: push (K, 4), one row of PUSH_ROWS per pushed environment; env_ids (K,) or None (every
+        environment, in order).  Refused before anything is copied: a table that is not (K, 4) or not finite, an id outside
+        [0, N), an id named twice.  A tensor on the device is read to the host for the check."""
+        N = self.cfg.num_envs
+        p = np.asarray(torch.as_tensor(push).detach().cpu(), dtype=np.float32)
+        if p.ndim != 2 or p.shape[1] != NUM_PUSH or p.shape[0] == 0:
+            raise ValueError(f"push: the table has to be (K, {NUM_PUSH}) with K >= 1, not {p.shape}")
+        if not np.isfinite(p).all():
+            raise ValueError("push: the table holds a value that is not finite")
+        K = int(p.shape[0])
+        if env_ids is None:
+            if K != N:
+                raise ValueError(f"push: a table without environment ids needs one row per environment ({N}), not {K}")
+            ids = None
+        else:
+            ids = np.asarray(torch.as_tensor(env_ids).cpu(), dtype=np.int64).reshape(-1)
+            if ids.size != K:
+                raise ValueError(f"push: {ids.size} environment ids for {K} rows")
+            if ids.min() < 0 or ids.max() >= N:
+                raise ValueError(f"push: environment ids have to lie in [0, {N})")
+            if np.unique(ids).size != ids.size:
+                raise ValueError("push: an environment is named twice")
+        self.env_ids = np.arange(N, dtype=np.int32) if ids is None else ids.astype(np.int32)
+        self.ids = None if ids is None else torch.from_numpy(self.env_ids).to(self.device)
+        self.table = torch.from_numpy(np.ascontiguousarray(p.T)).to(self.device)              # [4][K]
+        self.cfg.num_pushed = K
+        b = self.buf
+        b.root_states = self.buffers.root_states.data_ptr()
+        b.env_ids = self.ids.data_ptr() if self.ids is not None else None
+        b.push = self.table.data_ptr()
+
+    def launch(self):
+        """add the loaded table to the base velocities now (one launch, no sync): between two simulator steps"""
+        assert self.table is not None, "load() first"
+        self._check(self.lib.go1eval_push(ctypes.byref(self.cfg), ctypes.byref(self.buf), self._stream()), "go1eval_push")
