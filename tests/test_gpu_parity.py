@@ -16,11 +16,29 @@ ATTRIBUTED, in one of three checkable ways (a step attributed to precision alone
       (oracle/_build/libgo1oracle32.so, the same restatement with real = float) run beside the fp64 one and (ii), in the full-step runs,
       what perturbing the fp64 oracle's inputs by one fp32 ulp does to its own result (ShadowPert, three draws) — uses up a twentieth of a
       tolerance (the median of (i) is 0.3 %) AND comes within a factor 25 of the kernel's error (RULE_B_*): the state is ill-conditioned in
-      fp32 (deep interpenetration with kilonewton impulses, a non-converged 20-contact solve), whoever computes it.  (In bulk
-      the kernel's error equals the fp32 oracle's — finish() prints the ratio of the medians, 0.8-1.0 on the MI355X, and the
-      99 % quantiles coincide; in an ill-conditioned step the two are different draws from a heavy-tailed amplification of two
-      different rounding sequences, hence the factor.)
+      fp32 (deep interpenetration with kilonewton impulses, a non-converged 20-contact solve), whoever computes it.  (In an
+      ill-conditioned step the two are different draws from a heavy-tailed amplification of two different rounding sequences,
+      hence the factor.)
 tests/test_oracle_precision.py measures the rate at which the fp32 oracle alone leaves the tolerances: the same order.
+
+INSIDE the tolerances the kernel's error equals the fp32 oracle's, and finish() GATES that (the rules above cannot see a kernel 30 x less
+accurate everywhere, or in one quantity: the bulk sits at 0.001-0.015 of a tolerance): per compared quantity, over the environment-steps both
+fp32 evaluations are inside the tolerances in,
+    median_kernel <= max(1.5 median_fp32oracle, floor)   in lines of >= 256 environment-steps,
+    q99_kernel    <= max(2 q99_fp32oracle, floor)        in lines of >= 5000,
+the fp32 oracle being the one stepped beside the kernel on the same inputs and the floor the smaller of RULE_B_FLOOR and four fp32 ulps of
+the reference value in units of the tolerance (BULK_* below).  The per-quantity table is printed after every summary line and logged
+with it (profiles/parity_bulk.txt); a quantity may be left out of one line's gate only with its reason written there, two per line at most and
+never root_states, dof_pos, dof_vel, contact_forces, rew_buf, torques, obs_buf.  tests/test_parity_gate.py shows on the CPU that the gate
+passes a second valid fp32 evaluation and fails one whose error is three times as large, naming the quantity.  What the floor leaves unseen:
+dof_pos and rew_buf are good to about ONE fp32 ulp in either evaluation (1e-4 and 1e-5 of their tolerances against floors of 1e-3 and 2.4e-3),
+so a loss of accuracy in them shows only from about x10 (dof_pos) and x30 upwards (rew_buf) — or sooner through dof_vel, root_states and
+obs_buf, which any error in q or in a reward input reaches.
+
+Contact forces (net force on each of the 17 bodies after the step's last substep, kept through a reset of the same step) are compared
+wherever a full step is: 5e-2 N + 1 % on the plane (FULL_STEP_TOL, the fuzz and the train / evaluation split), 0.5 N + 1 % on the relief
+(RELIEF_TOL, where the reason is given); one substep: 5e-2 N + 0.2 % (SUBSTEP_TOL).  test_contact_forces_after_a_full_step starts full steps
+from the one-substep tests' states so that feet, calves, thighs and hips are all loaded.
 
 The kernels the PRODUCT launches carry no signature code (csrc/go1sim.hip: go1_step_kernel / _hf / _walls; the `_sig` twins are
 separate template instances).  test_product_instances_match_oracle runs those three at BASELINE's 4096 environments against the
@@ -154,7 +172,7 @@ class ProductPair:
     """a product instance of the step kernel (no signature buffer) and its `_sig` twin, stepped from the same inputs"""
 
     def __init__(self, S, Bc, orc, keys):
-        self.Bc, self.orc, self.keys = Bc, orc, list(keys) + ["contact_forces", "reset_buf", "time_out_buf"]
+        self.Bc, self.orc, self.keys = Bc, orc, list(dict.fromkeys(list(keys) + ["contact_forces", "reset_buf", "time_out_buf"]))
         self.Bg, self.sim = to_gpu(S, Bc, product=True)
         self.Bt, self.sim_t = to_gpu(S, Bc)
         self.env_steps = self.differ = 0
@@ -205,10 +223,45 @@ ATTRIBUTED_RATE = 5e-3           # fraction of environment-steps allowed to be a
                                  # staircase with kilonewton depenetration impulses: 2.4e-3; fp32-vs-fp64 oracle alone: 3e-5 .. 2e-3)
 
 
-class Attribution:
-    """Per-step bookkeeping of the environments outside the tolerances: every one must differ in its contact signature."""
+# The BULK gate (finish()): per quantity, over the environment-steps INSIDE the tolerances (the ones outside have the rules above), the
+# kernel's error statistics against those of the fp32 build of the oracle stepped beside it on the same inputs — never against the kernel's
+# own past values.  Median factor 1.5: the review's figure (the ratio of the medians of the per-environment maximum is 0.7-1.1 on all 31
+# lines of profiles/r06_parity_rates.txt); 99 % quantile factor 2: over the record's worst of 1.55 ("callbacks") among lines of >= 10,000
+# environment-steps.  Sample minimums: 256 for a median; 5000 for a 99 % quantile (>= 50 samples above it: the record's 252-step "ragged"
+# line shows 0.119 against 0.031 with two or three).
+BULK_MEDIAN_FACTOR, BULK_MEDIAN_MIN_STEPS = 1.5, 256
+BULK_Q99_FACTOR, BULK_Q99_MIN_STEPS = 2.0, 5000
+# Below what is an excess no evidence?  Never above RULE_B_FLOOR (0.05 of a tolerance); and — the bulk medians being 0.001-0.015 of a tolerance, a
+# floor of 0.05 alone would hide a kernel 3-30 x less accurate than the fp32 oracle, which is what the gate is for (tests/test_parity_gate.py
+# scales the error by 3) — never above BULK_FLOOR_ULPS fp32 ulps of the reference value itself, in units of the quantity's tolerance
+# (Attribution.ratio): two valid fp32 evaluations of a handful of operations differ by that much whoever computes them (a fused
+# multiply-add rounds once where two instructions round twice, sinf of the device against libm's: 1-2 ulp), and where the fp32 oracle
+# happens to be EXACT (a copied command, a drawn parameter) its statistic is 0 and no factor helps.  The value counts as 1 at least: a
+# quantity that is a DIFFERENCE of O(1) values in SI units (joint_pos_err_last = target - q, q up to 2.7 rad) carries the rounding of its
+# operands, and q itself is good to ONE ulp in either fp32 evaluation (measured, fp32 oracle: median error of dof_pos 1e-7 rad) — 1 ulp
+# against 2 is no loss of accuracy.  For qd, forces, torques, root state that is 1e-5 .. 3e-4 of a tolerance: far below their medians.
+BULK_FLOOR_ULPS = 4.0
+# A quantity whose excess is explained from the code as benign may be left out of the gate for ONE line, the reason written where the
+# line's Attribution is made (and printed in the table): at most BULK_MAX_EXCLUDED per line, and never one of these
+BULK_NEVER_EXCLUDED = ("root_states", "dof_pos", "dof_vel", "contact_forces", "rew_buf", "torques", "obs_buf")
+BULK_MAX_EXCLUDED = 2
 
-    def __init__(self, N, residual=(0, 0.0)):
+
+def _quantile(x, q):
+    """torch.quantile's linear interpolation over a sorted copy (torch.quantile itself refuses more than 16 M elements)"""
+    x = x.double().sort().values
+    pos = q * (x.numel() - 1)
+    lo = int(pos)
+    hi = min(lo + 1, x.numel() - 1)
+    a, b = float(x[lo]), float(x[hi])
+    return a if a == b else a + (b - a) * (pos - lo)          # (a == b: also inf, inf)
+
+
+class Attribution:
+    """Per-step bookkeeping of the environments outside the tolerances: every one must differ in its contact signature.  Of the ones
+    inside, the per-quantity error of kernel and fp32 oracle is kept for the bulk gate of finish()."""
+
+    def __init__(self, N, residual=(0, 0.0), bulk_exclude=None):
         """residual = (count, bound): at most `count` environment-steps of the whole run may stay UNEXPLAINED — outside a tolerance by at
         most `bound` x, none of the rules applying — instead of failing at the first one.  (0, 0) in every test of this file: nothing
         unexplained is admitted (the mechanism exists for investigations: tools/debug/hf_env_replay.py grew out of one)."""
@@ -218,6 +271,11 @@ class Attribution:
         self.residual, self.unexplained = residual, 0
         self.by_rule = {k: 0 for k in ("c", "a-list", "a-active", "local", "b-fp32", "b-pert")}
         self.worst_by_rule = {k: 0.0 for k in self.by_rule}
+        # bulk gate: per-quantity error / tolerance of the environment-steps inside the tolerances, one (Q, n) block per step
+        self.q_names, self.q_kernel, self.q_fp32, self.q_ulp = None, [], [], []
+        self.bulk_exclude = dict(bulk_exclude or {})          # quantity -> the reason it is left out of this line's gate
+        assert len(self.bulk_exclude) <= BULK_MAX_EXCLUDED and not set(self.bulk_exclude) & set(BULK_NEVER_EXCLUDED), self.bulk_exclude
+        self.bulk_failures = []                               # (quantity, statistic, kernel, fp32 oracle, bound) of finish()
 
     def _sig_words(self, Bc, Bx, words):
         """(N,) bool: the contact signatures differ in one of the listed words (include/go1sim.h GO1_SIG_WORDS) of some substep"""
@@ -225,21 +283,32 @@ class Attribution:
         rows = [r for r in range(a.shape[0]) if r % 4 in words]
         return (a[rows] != b[rows]).any(0)
 
-    def ratio(self, a, b, atol, rtol=0.0, env_dim=-1):
+    def ratio(self, a, b, atol, rtol=0.0, env_dim=-1, ulp=False):
+        """(N,) worst |a - b| / (atol + rtol |b|) of every environment; ulp: also, reduced the same way, what BULK_FLOOR_ULPS fp32 ulps of the
+        reference value b are in the same units (the bulk gate's floor), computed while b is on the device anyway"""
         dev = "cuda" if (a.is_cuda or b.is_cuda) else "cpu"          # (the arithmetic of the CHECK runs where the data is: 4096-env histories)
         a, b = a.to(dev).double(), b.to(dev).double()
-        r = (a - b).abs() / (atol + rtol * b.abs())
+        tol = atol + rtol * b.abs()
+        r = (a - b).abs() / tol
         r = torch.nan_to_num(r, nan=float("inf"))
-        if env_dim == 0:
-            return r.reshape(self.N, -1).max(1).values.cpu()
-        return r.reshape(-1, self.N).max(0).values.cpu()
+        per_env = (lambda t: t.reshape(self.N, -1).max(1).values.cpu()) if env_dim == 0 else (lambda t: t.reshape(-1, self.N).max(0).values.cpu())
+        if ulp:
+            return per_env(r), per_env(torch.nan_to_num(b.abs().clamp_min(1.0) * (BULK_FLOOR_ULPS * 2.0 ** -23) / tol, nan=0.0, posinf=0.0))
+        return per_env(r)
 
     def step(self, ratio_fn, Bg, Bc, B32=None, reset_key=None, also_attributed=None, twin=None, pert=None):
         """ratio_fn(Bx, Bref) -> (N,) worst error / tolerance of every environment this step; B32: the fp32 oracle's buffers;
         reset_key: a buffer whose mismatch (termination decided differently) puts the environment outside the tolerances;
         twin = (Bt, identical): Bg carries no signature (a product instance) — rule (a) reads the record of the `_sig` twin Bt for
         the environments whose outputs are bit-identical in the two (`identical`, (N,) bool)."""
-        ratio = ratio_fn(Bg, Bc)
+        per_quantity = getattr(ratio_fn, "per_quantity", None)     # (make_ratio's; a plain callable gives the per-environment maximum only)
+        assert per_quantity is not None or B32 is None, "beside the fp32 oracle the ratio function must be make_ratio's: the bulk gate needs per-quantity errors"
+        pq = pq32 = None
+        if per_quantity is not None:
+            pq, ulps = per_quantity(Bg, Bc, ulp=True)
+            ratio = pq.max(0).values
+        else:
+            ratio = ratio_fn(Bg, Bc)
         if twin is not None:
             assert Bg.contact_signature is None
             sig = (twin[0].contact_signature.cpu() != Bc.contact_signature).any(0) & twin[1]
@@ -260,7 +329,9 @@ class Attribution:
             # tolerance (printed by finish()), uses up RULE_B_FLOOR of it here AND is within RULE_B_FACTOR of the kernel's error;
             # (c): the kernel REPRODUCES the fp32 oracle within the tolerances (a decision both fp32 evaluations take the same
             # way and fp64 the other — e.g. a termination threshold): no bound on how far that is from the fp64 result
-            ratio32 = ratio_fn(B32, Bc)
+            pq32 = per_quantity(B32, Bc)
+            ratio32 = pq32.max(0).values
+            ratio32_own = ratio32                      # (before the perturbation probe below is folded in)
             same32_pre = ratio_fn(Bg, B32) <= 1.0
             rule_b32 = (ratio32 > RULE_B_FLOOR) & (ratio <= RULE_B_FACTOR * ratio32)
             need = bad & ~sig & ~(rule_b32 | same32_pre)
@@ -271,12 +342,20 @@ class Attribution:
                     if reset_key is not None:      # (a termination decided differently under the perturbation: a threshold sits here)
                         rp = torch.where(Bp.tensors[reset_key].bool() != Bc.tensors[reset_key].bool(), torch.full_like(rp, 1e3), rp)
                     ratio32 = torch.maximum(ratio32, rp)
-            same32 = ratio_fn(Bg, B32) <= 1.0
+            same32 = same32_pre.clone()                # (the perturbed oracles have buffers of their own: Bg and B32 are what they were)
             if reset_key is not None:
                 same32 = same32 & (Bg.tensors[reset_key].cpu().bool() == B32.tensors[reset_key].bool())
             rule_bp = (ratio32 > RULE_B_FLOOR) & (ratio <= RULE_B_FACTOR * ratio32) & ~rule_b32
             sig = sig | rule_b32 | rule_bp | same32
             self.r32_all.append(ratio32.clone()); self.r_all.append(ratio.clone())
+            # the bulk gate's samples: environment-steps in which BOTH fp32 evaluations are inside the tolerances (and decide the
+            # termination as the fp64 oracle does) — the others are the business of the rules
+            inside = ~bad & (ratio32_own <= 1.0)
+            if reset_key is not None:
+                inside = inside & (B32.tensors[reset_key].bool() == Bc.tensors[reset_key].bool())
+            assert self.q_names in (None, ratio_fn.names), (self.q_names, ratio_fn.names)
+            self.q_names = ratio_fn.names
+            self.q_kernel.append(pq[:, inside].float()); self.q_fp32.append(pq32[:, inside].float()); self.q_ulp.append(ulps[:, inside].float())
         # who carries what (every out-of-tolerance environment-step is counted under the FIRST rule that explains it, in this order):
         #   c: the kernel reproduces the fp32 oracle within the tolerances (the strongest statement: the kernel IS a valid fp32 evaluation there,
         #   whatever fp64 decides — gpurun call r5c: a x2923 step on the relief where kernel and fp32 oracle agree to 1e-5 of it);
@@ -343,9 +422,12 @@ class Attribution:
         line = (f"{what}: {self.env_steps} env-steps, {self.bad} outside the tolerances, {res} "
                 f"(rate {rate:.2e}, worst x{self.worst_ratio:.1f} of the tolerance by precision alone{'; by rule: ' + split if split else ''}){q}{self.note}")
         print(line)
-        if os.environ.get("GO1_PARITY_LOG"):            # the GPU run's summaries, committed as profiles/r04_parity_rates.txt
+        table = self.bulk_table()
+        for row in table:
+            print(row)
+        if os.environ.get("GO1_PARITY_LOG"):            # the GPU run's summaries and per-quantity tables, committed as profiles/parity_bulk.txt
             with open(os.environ["GO1_PARITY_LOG"], "a") as f:
-                f.write(line + "\n")
+                f.write("\n".join([line] + table) + "\n")
         assert rate <= ATTRIBUTED_RATE, rate
         assert self.worst_ratio <= ATTRIBUTED_BOUND, self.worst_ratio
         # rule (a) has its own bound and the active-set-only part of it its own rate (a solver regression would show up THERE: same lists,
@@ -354,6 +436,44 @@ class Attribution:
         n = max(self.env_steps, 1)
         assert self.by_rule["a-active"] / n <= RULE_A_ACTIVE_RATE, (self.by_rule, n)
         assert (self.by_rule["b-fp32"] + self.by_rule["b-pert"] + self.by_rule["c"]) / n <= RULE_BC_RATE, (self.by_rule, n)
+        # the bulk gate (BULK_* above): inside the tolerances the kernel is as accurate as the fp32 oracle, quantity by quantity
+        assert not self.bulk_failures, f"{what}: less accurate in bulk than the fp32 oracle beside it — " + "; ".join(
+            f"{k} {stat}: kernel {a:.5f} of its tolerance, fp32 oracle {b:.5f} (bound {bound:.5f})" for k, stat, a, b, bound in self.bulk_failures)
+
+    def bulk_table(self):
+        """One row per compared quantity — median and 99 % quantile of error / tolerance over the environment-steps inside the tolerances,
+        kernel and fp32 oracle, their ratios, the floor — and, in self.bulk_failures, what exceeds
+            median_kernel <= max(1.5 median_fp32oracle, floor)      (lines of >= 256 such environment-steps)
+            q99_kernel    <= max(2 q99_fp32oracle, floor)           (lines of >= 5000)
+        with floor = min(RULE_B_FLOOR, the same statistic of BULK_FLOOR_ULPS ulps of the reference value / tolerance)."""
+        self.bulk_failures = []
+        if not self.q_kernel:
+            assert not self.r_all          # (step() collects both or neither)
+            return ["  per quantity: NOT GATED (no fp32 oracle was stepped beside the kernel)"]
+        K, R, U = torch.cat(self.q_kernel, 1), torch.cat(self.q_fp32, 1), torch.cat(self.q_ulp, 1)
+        n = K.shape[1]
+        unknown = set(self.bulk_exclude) - set(self.q_names)
+        assert not unknown, unknown
+        rows = [f"  per quantity, {n} env-steps inside the tolerances: error / tolerance, median | 99 %: kernel, fp32 oracle, kernel / fp32 oracle, floor"]
+        if n == 0:
+            return rows
+        div = lambda a, b: f"{a / b:.2f}" if b > 0 else ("1.00" if a == 0 else "inf")
+        for i, k in enumerate(self.q_names):
+            stats = [(_quantile(K[i], q), _quantile(R[i], q), min(RULE_B_FLOOR, _quantile(U[i], q))) for q in (0.5, 0.99)]
+            verdict = []
+            for (stat, factor, least), (a, b, floor) in zip((("median", BULK_MEDIAN_FACTOR, BULK_MEDIAN_MIN_STEPS), ("99 %", BULK_Q99_FACTOR, BULK_Q99_MIN_STEPS)), stats):
+                bound = max(factor * b, floor)
+                if n >= least and not a <= bound:
+                    verdict.append(f"{stat} ABOVE {bound:.5f}")
+                    if k not in self.bulk_exclude:
+                        self.bulk_failures.append((k, stat, a, b, bound))
+            gated = "median + 99 %" if n >= BULK_Q99_MIN_STEPS else "median" if n >= BULK_MEDIAN_MIN_STEPS else "not gated (too few)"
+            if k in self.bulk_exclude:
+                gated = f"EXCLUDED from the gate: {self.bulk_exclude[k]}"
+            (mk, mr, mf), (qk, qr, qf) = stats
+            rows.append(f"    {k:<26} kernel {mk:.5f} | {qk:.5f}   fp32 oracle {mr:.5f} | {qr:.5f}   ratio {div(mk, mr)} | {div(qk, qr)}   floor {mf:.5f} | {qf:.5f}   "
+                        f"{gated}{' — ' + ', '.join(verdict) if verdict else ''}")
+        return rows
 
 
 def grazing_collision_count(att, Bg, Bc, keys, rows=()):
@@ -374,23 +494,24 @@ SUBSTEP_TOL = (("root_states", 2e-4, 1e-4), ("dof_pos", 2e-4, 1e-4), ("dof_vel",
 
 
 def make_ratio(att, keys, rows=()):
-    """ratio_fn for Attribution.step over [C][N] quantities `keys` and (N, K) row-major ones `rows`: (name, atol, rtol)"""
+    """ratio_fn for Attribution.step over [C][N] quantities `keys` and (N, K) row-major ones `rows`: (name, atol, rtol).
+    fn(Bx, Bref) -> (N,) the worst error / tolerance of every environment; fn.per_quantity(Bx, Bref) -> (Q, N) the same per quantity
+    (fn.names, keys then rows), of which fn() is the maximum — every quantity is compared ONCE per call."""
+    spec = [(k, tol, rt, -1) for k, tol, rt in keys] + [(k, tol, rt, 0) for k, tol, rt in rows]
+
+    def per_quantity(Bx, Bref, ulp=False):
+        out = [att.ratio(Bx.tensors[k], Bref.tensors[k], tol, rt, env_dim=d, ulp=ulp) for k, tol, rt, d in spec]
+        if ulp:
+            return torch.stack([r for r, _ in out]), torch.stack([u for _, u in out])
+        return torch.stack(out)
+
     def fn(Bx, Bref):
-        ratio = torch.zeros(att.N, dtype=torch.float64)
-        for k, tol, rt in keys:
-            ratio = torch.maximum(ratio, att.ratio(Bx.tensors[k], Bref.tensors[k], tol, rt))
-        for k, tol, rt in rows:
-            ratio = torch.maximum(ratio, att.ratio(Bx.tensors[k], Bref.tensors[k], tol, rt, env_dim=0))
-        return ratio
+        return per_quantity(Bx, Bref).max(0).values
 
     def detail(Bx, Bref, mask):
-        out = {}
-        for k, tol, rt in keys:
-            out[k] = round(float(att.ratio(Bx.tensors[k], Bref.tensors[k], tol, rt)[mask].max()), 2)
-        for k, tol, rt in rows:
-            out[k] = round(float(att.ratio(Bx.tensors[k], Bref.tensors[k], tol, rt, env_dim=0)[mask].max()), 2)
-        return {k: v for k, v in out.items() if v > 0.5}
-    fn.detail = detail
+        worst = per_quantity(Bx, Bref)[:, mask].max(1).values
+        return {k: round(float(v), 2) for (k, _, _, _), v in zip(spec, worst) if v > 0.5}
+    fn.per_quantity, fn.names, fn.detail = per_quantity, [k for k, _, _, _ in spec], detail
     return fn
 
 
@@ -469,7 +590,11 @@ FULL_STEP_TOL = (("root_states", 1e-3, 1e-3), ("dof_pos", 1e-3, 0), ("dof_vel", 
                  ("motor_strengths", 1e-6, 0), ("last_actions", 1e-6, 0),
                  # state the torque model carries (LDS stash in the step kernel, written back once per step)
                  ("joint_pos_err_last", 1e-3, 0), ("joint_pos_err_last_last", 1e-3, 0), ("joint_vel_last", 2e-2, 1e-3),
-                 ("joint_vel_last_last", 2e-2, 1e-3), ("joint_pos_target", 1e-5, 0), ("lag_buffer", 1e-5, 0))
+                 ("joint_vel_last_last", 2e-2, 1e-3), ("joint_pos_target", 1e-5, 0), ("lag_buffer", 1e-5, 0),
+                 # net contact force of every body after the step's LAST substep (what legged_robot.py reads as contact_forces): the one-substep
+                 # absolute part with the relative part of the full step.  fp32 oracle against fp64 oracle on the plane (train_noise, 15,360
+                 # env-steps, feet / calves / thighs / a hip loaded up to 1.2 kN): median 0.0013, 99 % 0.011, worst 0.25 of it, none outside
+                 ("contact_forces", 5e-2, 1e-2))
 ROW_TOL = (("obs_buf", 3e-3, 1e-3), ("privileged_obs_buf", 1e-5, 0), ("obs_history", 3e-3, 1e-3))
 
 
@@ -577,7 +702,8 @@ def test_full_step_under_random_configurations(case):
         sim.step(torch.from_numpy(a).cuda())
         torch.cuda.synchronize()
         keys = (("root_states", 1e-3, 1e-3), ("dof_pos", 1e-3, 0), ("dof_vel", 2e-2, 1e-3), ("rew_buf", 2e-4, 1e-3),
-                ("commands", 1e-5, 0), ("torques", 5e-3, 1e-3), ("episode_sums", 1e-3, 1e-3), ("command_sums", 1e-3, 1e-3))
+                ("commands", 1e-5, 0), ("torques", 5e-3, 1e-3), ("episode_sums", 1e-3, 1e-3), ("command_sums", 1e-3, 1e-3),
+                ("contact_forces", 5e-2, 1e-2))
         rows = (("obs_buf", 3e-3, 1e-3), ("privileged_obs_buf", 3e-3, 1e-3))
         att.step(make_ratio(att, keys, rows), Bg, Bc, sh.B, reset_key="reset_buf")
         sync_from(Bc, Bg, sim, orc)
@@ -745,10 +871,9 @@ def test_physics_substep_on_height_field(scenario, walls):
     assert wall_contacts == 0 if not walls else (wall_contacts > 0 or scenario == "standing"), wall_contacts       # the vertical faces were hit
 
 
-def run_height_field_comparison(walls, N=256, steps=40, product=False, residual=(0, 0.0), alt=False):
-    """full steps on the rough int16 height field of rough_field(): 187-point height scan in the observation, resets onto the
-    field, the height-relative termination test (legged_robot.py:160-178, 1793-1806); walls: as a `trimesh` terrain (vertical
-    risers).  product: the instance the product launches (no signature code) beside its `_sig` twin."""
+def relief_pair(walls, N, alt=False):
+    """configuration, buffers and fp64 oracle of the full-step runs on the relief: train_noise with the 187-point height scan observed,
+    rough_field() bound as a height field (walls: as a `trimesh` terrain), the robots reset onto it"""
     pts_x = [round(-0.8 + 0.1 * i, 1) for i in range(17)]
     pts_y = [round(-0.5 + 0.1 * i, 1) for i in range(11)]
     ex = {"terrain": dict(measure_heights=True, measured_points_x=pts_x, measured_points_y=pts_y),
@@ -767,13 +892,37 @@ def run_height_field_comparison(walls, N=256, steps=40, product=False, residual=
     Bc.env_origins[2] = torch.from_numpy(hs.astype(np.float32))[ix, iy] * vscale + 0.05
     orc = pyoracle.Oracle(S, Bc)
     orc.reset_idx()
+    return S, Bc, orc
+
+
+# the relief's tolerances (root 3e-3, torques 2e-2: reasons in run_height_field_comparison).  Contact forces 0.5 N here, 5e-2 on the plane: with
+# 5e-2 the fp32 ORACLE alone leaves the force tolerance, everything else inside, in 22 of 15,360 environment-steps on this relief (8 with
+# walls) = 1.4e-3, which on top of the 2.9e-3 the 4096-environment relief line already uses of RULE_BC_RATE = 4e-3 would breach the frozen
+# rate; with 0.5 N: 4 and 0 (tests/test_oracle_precision.py measures them)
+RELIEF_TOL = (("root_states", 3e-3, 1e-3), ("dof_pos", 1e-3, 0), ("dof_vel", 2e-2, 1e-3), ("rew_buf", 2e-4, 1e-3),
+              ("torques", 2e-2, 1e-3), ("foot_positions", 1e-3, 0), ("contact_forces", 0.5, 1e-2), ("measured_heights", 1e-3, 0))
+
+
+def height_scan_flip(att, Bg, Bc, keys):
+    """test-local rule of the relief's full-step tests (see where it is used): (N,) bool, at most 4 of the 187 scan heights differ and nothing else"""
+    assert keys[-1][0] == "measured_heights"
+    scan_pts = ((Bg.measured_heights.cpu() - Bc.measured_heights).abs() > 1e-3).sum(0)
+    core = make_ratio(att, keys[:-1])(Bg, Bc)
+    prop = att.ratio(Bg.obs_buf[:, :70].contiguous(), Bc.obs_buf[:, :70].contiguous(), 5e-3, 1e-3, env_dim=0)
+    return (scan_pts > 0) & (scan_pts <= 4) & (core <= 1.0) & (prop <= 1.0)
+
+
+def run_height_field_comparison(walls, N=256, steps=40, product=False, residual=(0, 0.0), alt=False):
+    """full steps on the rough int16 height field of rough_field(): 187-point height scan in the observation, resets onto the
+    field, the height-relative termination test (legged_robot.py:160-178, 1793-1806); walls: as a `trimesh` terrain (vertical
+    risers).  product: the instance the product launches (no signature code) beside its `_sig` twin."""
+    S, Bc, orc = relief_pair(walls, N, alt)
     # (root 3e-3 here: on the relief the contact normals are the bilinear interpolant's gradient AT the contact point, so a
     #  round-off sized shift of the point tilts the whole contact frame — the flat-terrain tests keep 1e-3)
     # (torques 2e-2: the actuator network's gain on the PREVIOUS substep's position error is 17 N m/rad on average, 23 at the
     #  99 % quantile (finite differences of oracle/pyoracle.actuator_net), so a q inside its 1e-3 tolerance already moves the
     #  torque by 2e-2 N m; the flat-terrain tests keep 5e-3 because q agrees to 1e-4 there)
-    keys = (("root_states", 3e-3, 1e-3), ("dof_pos", 1e-3, 0), ("dof_vel", 2e-2, 1e-3), ("rew_buf", 2e-4, 1e-3),
-            ("torques", 2e-2, 1e-3), ("foot_positions", 1e-3, 0), ("measured_heights", 1e-3, 0))
+    keys = RELIEF_TOL
     pp = ProductPair(S, Bc, orc, [k for k, _, _ in keys] + ["obs_buf", "obs_history"]) if product else None
     Bg, sim = (pp.Bg, pp.sim) if product else to_gpu(S, Bc)
     pp.sync() if product else sync_from(Bc, Bg, sim, orc)
@@ -797,10 +946,7 @@ def run_height_field_comparison(walls, N=256, steps=40, product=False, residual=
         # A scan point within round-off of a cell boundary reads the neighbouring sample in fp32 (legged_robot.py:1793-1806 floors
         # (x + border) / scale): environments whose ONLY differences are a few of the 187 scan heights (and their observation
         # columns) are attributed to that — the rest of their state, rewards and the 70 proprioceptive columns must agree
-        scan_pts = ((Bg.measured_heights.cpu() - Bc.measured_heights).abs() > 1e-3).sum(0)
-        core = make_ratio(att, keys[:-1])(Bg, Bc)
-        prop = att.ratio(Bg.obs_buf[:, :70].contiguous(), Bc.obs_buf[:, :70].contiguous(), 5e-3, 1e-3, env_dim=0)
-        scan_flip = (scan_pts > 0) & (scan_pts <= 4) & (core <= 1.0) & (prop <= 1.0)
+        scan_flip = height_scan_flip(att, Bg, Bc, keys)
         att.step(make_ratio(att, keys, (("obs_buf", 5e-3, 1e-3),)), Bg, Bc, sh.B, reset_key="reset_buf", also_attributed=scan_flip, twin=twin, pert=sp)
         resets += int(cpu_reset.sum())
         pp.sync() if product else sync_from(Bc, Bg, sim, orc)
@@ -819,6 +965,76 @@ def test_full_step_on_height_field(walls):
     """40 full steps with the 187-point height scan in the observation, resets onto the field and the
     height-relative termination test (legged_robot.py:160-178, 1793-1806); walls: as a `trimesh` terrain (vertical risers)."""
     run_height_field_comparison(walls)
+
+
+FORCE_CASES = [("standing", False), ("dropped", False), ("tumbling", False), ("tumbling", True)]
+
+
+def test_contact_forces_after_a_full_step():
+    """contact_forces as legged_robot.py reads it — net_contact_force of every body after the step's LAST substep, kept through a reset of the
+    same step — compared after FULL steps, from the start states of the one-substep tests imposed anew before every step (standing, dropped
+    onto / into the plane, tumbling; tumbling also over the relief with walls, half of the robots over the staircase strip): 256 environments
+    x 6 steps per case, FULL_STEP_TOL / ROW_TOL (relief: RELIEF_TOL), through Attribution with the fp32 oracle beside.  Not vacuous: in the oracle
+    feet, calves, thighs and hips each carry more than 1 N, on the walls a horizontal component more than 0.5 N."""
+    N, steps = 256, 6
+    groups = {"hip": [1, 5, 9, 13], "thigh": [2, 6, 10, 14], "calf": [3, 7, 11, 15], "foot": [4, 8, 12, 16]}
+    for scenario, walls in FORCE_CASES:
+        if walls:
+            S, Bc, orc = relief_pair(True, N)
+            hs, hscale, vscale = rough_field(seed=2)
+            keys, rows = RELIEF_TOL, (("obs_buf", 5e-3, 1e-3),)
+        else:
+            cfg, S, meta, Bc, orc = gpu_pair("train_noise", N, seed=11)
+            keys, rows = FULL_STEP_TOL, ROW_TOL
+        g = torch.Generator().manual_seed(6)
+        rng = np.random.default_rng(6)
+        Bg, sim = to_gpu(S, Bc)
+        sh = Shadow32(S, Bc, orc)
+        att = Attribution(N)
+        loaded = {k: 0 for k in groups}
+        side, resets = 0.0, 0
+        for step in range(steps):
+            if scenario != "tumbling":
+                standing_state(S, Bc, z=0.28)
+            if scenario == "dropped":
+                Bc.root_states[2].uniform_(0.05, 0.3, generator=g)      # some start interpenetrating: depenetration path
+                Bc.root_states[9] = -1.5                                # restitution path
+            if scenario == "tumbling":
+                q = torch.randn(4, N, generator=g)
+                Bc.root_states[3:7] = q / q.norm(dim=0, keepdim=True)
+                Bc.root_states[0:2] = 0.0
+                Bc.root_states[2].uniform_(0.08, 0.35, generator=g)
+                Bc.root_states[7:13].uniform_(-2, 2, generator=g)
+                Bc.dof_vel.uniform_(-5, 5, generator=g)
+            if walls:                                                   # onto the field, every second robot over the staircase strip
+                clearance = Bc.root_states[2].clone()
+                scatter_on_field(S, Bc, g, hs, hscale, vscale, 0.0)
+                Bc.root_states[1, ::2].uniform_(10.2, 13.8, generator=g)
+                ix, iy = (Bc.root_states[0] / hscale).long(), (Bc.root_states[1] / hscale).long()
+                Bc.root_states[2] = torch.from_numpy(hs.astype(np.float32))[ix, iy] * vscale + clearance
+            sync_from(Bc, Bg, sim, orc)
+            sh.sync()
+            a = (rng.standard_normal((N, 12)) * (1.0 if step % 2 else 0.3)).astype(np.float32)
+            orc.step(a)
+            sh.o.step(a)
+            sim.step(torch.from_numpy(a).cuda())
+            torch.cuda.synchronize()
+            local = height_scan_flip(att, Bg, Bc, keys) if walls else grazing_collision_count(att, Bg, Bc, keys, rows)
+            att.step(make_ratio(att, keys, rows), Bg, Bc, sh.B, reset_key="reset_buf", also_attributed=local)
+            cf = Bc.contact_forces.view(17, 3, N)
+            for k, bodies in groups.items():
+                loaded[k] += int((cf[bodies].norm(dim=1) > 1.0).sum())
+            side = max(side, float(cf[:, :2].abs().max()))
+            resets += int(Bc.reset_buf.sum())
+        assert int(Bg.fault_counts[:10].sum()) == 0, Bg.fault_counts.tolist()
+        att.finish(f"contact forces after a full step [{scenario}{', walls' if walls else ''}, {N} envs x {steps} steps; body-steps above 1 N: "
+                   f"{', '.join(f'{k} {v}' for k, v in loaded.items())}; {resets} resets]")
+        assert "contact_forces" in att.q_names and att.env_steps == N * steps
+        assert loaded["foot"] > N, loaded
+        if scenario == "tumbling":                                      # every kind of body lands, and robots that terminate carry their forces through the reset
+            assert min(loaded.values()) > 20 and resets > 20, (loaded, resets)
+        if walls:
+            assert side > 0.5, side
 
 
 # (instance, environments, steps, alt): the three instances at configs[1] / [2]'s 4096 environments; round 6 (the review of round 5): plane and walls at
@@ -1034,10 +1250,19 @@ def test_train_eval_split_matches_oracle():
     sh.o.set_eval_config(S_eval, NT)
     rng = np.random.default_rng(2)
     train_resets = 0
-    att = Attribution(N)          # no free budget: an environment outside the tolerances must be attributed (module docstring)
+    # no free budget: an environment outside the tolerances must be attributed (module docstring).
+    # Left out of this line's bulk gate: friction_coeffs.  It is the quantity behind the 99 % quantile of 0.238 against the fp32 oracle's 0.008
+    # in profiles/r06_parity_rates.txt.  randomize_rigid_props (csrc/go1_maps.h, oracle/go1_oracle.c) draws u (hi - lo) + lo in fp32 in BOTH
+    # builds of the oracle — two roundings, identical, error 0 — and the HIP build, by hipcc's default -ffp-contract=fast for device code, contracts
+    # it into one fused multiply-add (INFERRED from the sources, the size of the difference and the emulator, not read off the ISA): where the product is
+    # inexact (the training group's range [0.1, 3.0]; the evaluation group's 0.5 u + 5 is exact) the result is the neighbouring float in 3 % of the
+    # draws — one ulp of a value in [2, 4) = 2.38e-7 against an absolute tolerance of 1e-6 (the fused one is the better rounded; the
+    # emulated kernel, compiled without contraction, gives 0).  payloads (4 u - 1: exact product) and the others drawn here stay gated.
+    att = Attribution(N, bulk_exclude={"friction_coeffs": "one fp32 ulp of a re-drawn value in [2, 4) (u (hi - lo) + lo fused into one multiply-add "
+                                                          "by the HIP build, two roundings in both oracle builds) = 0.238 of the absolute tolerance 1e-6"})
     keys = (("root_states", 1e-3, 1e-3), ("dof_pos", 1e-3, 0), ("friction_coeffs", 1e-6, 0), ("restitutions", 1e-6, 0),
             ("payloads", 1e-6, 0), ("motor_strengths", 1e-6, 0), ("motor_offsets", 1e-6, 0), ("rew_buf", 2e-4, 1e-3),
-            ("commands", 1e-5, 0), ("episode_sums", 1e-3, 1e-3), ("episode_sums_eval", 1e-3, 1e-3))
+            ("commands", 1e-5, 0), ("episode_sums", 1e-3, 1e-3), ("episode_sums_eval", 1e-3, 1e-3), ("contact_forces", 5e-2, 1e-2))
     for step in range(40):
         a = (rng.standard_normal((N, 12)) * 0.5).astype(np.float32)
         Bg.episode_log.zero_()
