@@ -1,7 +1,11 @@
 """The product's DEVICE CODE (walk-these-ways_amd/csrc/*.h, go1sim.hip — unmodified) executed lane by lane on the CPU by the
 SIMT emulator of tests/emu, against the fp64 oracle and against the reference-generated fixtures.  These are the same
 comparisons as the `-m gpu` parity tests at sizes the emulator finishes in seconds; they run where there is no GPU (here
-and in the driver's CPU tier).  The emulator is test infrastructure: the product only ever loads csrc/libgo1sim.so."""
+and in the driver's CPU tier).  The emulator is test infrastructure: the product only ever loads csrc/libgo1sim.so.
+
+The self-collision, thigh-capsule, hip-capsule, limit-row and contact-heavy tests take their inputs and event counters from tests/scenarios.py;
+tests/test_gpu_scenarios.py runs the same builders on the compiled kernel (the emulator implements DPP, the barriers and the LDS hand-overs
+from a reading of them and computes without the HIP build's contraction: a pass here says the SOURCE is right).  Each prints its event counts."""
 import os
 import sys
 
@@ -11,10 +15,10 @@ import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "emu"))
 import go1sim_host as H  # noqa: E402
+import scenarios  # noqa: E402
 from test_gpu_parity import ATTRIBUTED_BOUND, RULE_B_FACTOR, RULE_B_FLOOR  # noqa: E402  (constants only: that module's tests need the GPU)
 from golden.variants import FUZZ_VARIANTS, random_switches  # noqa: E402
 from util import (GOLDEN, RESAMPLE_MODES, check_resample_against_reference, load_maps_fixture, load_resample_fixture, maps_fixture_stream, maps_keep,  # noqa: E402
-                  self_contacts_listed, self_pair_codes,
                   make_sim, randomize_dr, standing_state)
 
 
@@ -34,6 +38,19 @@ def pair(oracle_lib, emu, variant, N, seed=3, signature=False, **kw):
     orc.reset_idx()
     Be = Bc.clone_to("cpu")
     return S, Bc, orc, Be, emu.EmuSim(S, Be)
+
+
+def scenario_pair(oracle_lib, emu, name, signature=True):
+    """a free-flight scenario of tests/scenarios.py (the inputs tests/test_gpu_scenarios.py runs on the MI355X), the fp64 oracle on its
+    buffers and the emulated kernel on a copy; signature=False: the copy carries no signature buffer, so the emulator runs the instance
+    without the signature code (the oracle keeps its record: the event counters read it)"""
+    sc = scenarios.FREE_FLIGHT[name]()
+    orc = oracle_lib.Oracle(sc.S, sc.Bc)
+    Be = sc.Bc.clone_to("cpu")
+    if not signature:
+        Be.tensors["contact_signature"] = None
+        Be.refresh_struct()
+    return sc, sc.Bc, orc, Be, emu.EmuSim(sc.S, Be)
 
 
 def resync(Bc, Be, sim, orc):
@@ -150,30 +167,21 @@ def test_emulated_limit_rows_conserve_momentum_and_match_oracle(oracle_lib, emu)
     """The root-cause scenario of round 1's non-finite rewards through the KERNEL code: zero gravity, free flight, 20 N m
     held against the hip velocity limit / the thigh stops.  The limit rows keep the base at rest (before: 1450 rad/s after
     50 substeps) and the kernel follows the oracle to round-off, so the rows are the same rows."""
-    N = 16
-    cfg, S, meta, Bc = make_sim("train", N, extra={"domain_rand": dict(randomize_gravity=False)})
-    S.gravity[0] = S.gravity[1] = S.gravity[2] = 0.0
-    standing_state(S, Bc, z=5.0)
-    Bc.torques.zero_()
-    Bc.torques[[0, 3, 6, 9], 0:4] = 20.0
-    Bc.torques[[1, 4, 7, 10], 4:8] = -20.0
-    Bc.torques[:, 8:12] = torch.tensor([20.0, -20.0, 20.0] * 4).unsqueeze(1)
-    Bc.dof_vel[[0, 3, 6, 9], 12:16] = 30.0
-    orc = oracle_lib.Oracle(S, Bc)
-    Be = Bc.clone_to("cpu")
-    sim = emu.EmuSim(S, Be)
-    for it in range(120):
+    sc, Bc, orc, Be, sim = scenario_pair(oracle_lib, emu, "limit_rows", signature=False)
+    ctr = scenarios.KernelCounters()                     # (resync() overwrites the kernel's fault counters with the oracle's zeros)
+    for it in range(sc.substeps):
         orc.physics_substep()
         sim.physics_substep()
         for k, tol in (("root_states", 5e-4), ("dof_pos", 1e-4), ("dof_vel", 2e-2)):
             assert diff(Be, Bc, k) <= tol, (it, k, diff(Be, Bc, k))
+        sc.events.substep(Bc)
+        ctr.add(Be, Bc)
         resync(Bc, Be, sim, orc)
+    print("events[limit_rows]", sc.events.free_flight())
     assert torch.isfinite(Be.root_states).all()
     assert float(Be.root_states[10:13, :12].norm(dim=0).max()) < 3.0 and float(Be.root_states[7:10, :12].norm(dim=0).max()) < 1.0
-    lo = torch.tensor([-0.802851455917, -1.0471975512, -2.69653369433] * 4).unsqueeze(1)
-    hi = torch.tensor([0.802851455917, 4.18879020479, -0.916297857297] * 4).unsqueeze(1)
-    assert bool(((Be.dof_pos >= lo - 0.03) & (Be.dof_pos <= hi + 0.03)).all())
-    assert int(Be.fault_counts[:10].sum()) == 0 and int(Be.fault_counts[H.abi.GO1_FAULT_LIMIT_SAFETY]) == 0
+    assert bool(((Be.dof_pos >= scenarios.DOF_LO - 0.03) & (Be.dof_pos <= scenarios.DOF_HI + 0.03)).all())
+    assert int(ctr.faults[:10].sum()) == 0 and int(ctr.faults[H.abi.GO1_FAULT_LIMIT_SAFETY]) == 0, ctr.faults.tolist()
 
 
 @pytest.mark.parametrize("variant,fname", [("train", "maps_train.npz"), ("alt", "maps_alt_mild.npz"), ("alt2", "maps_alt2.npz"),
@@ -283,75 +291,44 @@ def test_emulated_self_collision_matches_oracle(oracle_lib, emu):
     """Self-collision through the KERNEL code: in free flight the hips swing the lower legs into each other (left-right and,
     with the thighs, front-rear) and fold the feet against the trunk; leg-leg rows carry two leg parts, trunk-leg rows one.
     Kernel and oracle agree to round-off on every substep, and contacts between bodies of the robot do occur."""
-    N = 16
-    cfg, S, meta, Bc = make_sim("train", N, extra={"domain_rand": dict(randomize_gravity=False)})
-    assert S.self_collision == 1
-    S.gravity[0] = S.gravity[1] = S.gravity[2] = 0.0
-    standing_state(S, Bc, z=3.0)
-    g = torch.Generator().manual_seed(5)
-    Bc.torques.zero_()
-    Bc.torques[[0, 6]] = -1.0
-    Bc.torques[[3, 9]] = 1.0                                   # hips: left and right legs towards each other
-    Bc.torques[[1, 4], 4:8] = 1.5                              # envs 4-7: front thighs back ...
-    Bc.torques[[7, 10], 4:8] = -1.5                            # ... rear thighs forward: front-rear pairs
-    Bc.torques[[0, 3, 6, 9], 4:8] = 0.0
-    Bc.torques[[2, 5, 8, 11], 8:12] = -3.0                     # envs 8-11: calves fold up, thighs swing the feet to the belly
-    Bc.torques[[1, 4, 7, 10], 8:12] = torch.tensor([3.0, 3.0, -3.0, -3.0]).unsqueeze(1)
-    Bc.torques[[0, 3, 6, 9], 8:12] = 0.0
-    Bc.torques[:, 12:16] = torch.empty(12, 4).uniform_(-2.0, 2.0, generator=g)
-    orc = oracle_lib.Oracle(S, Bc)
-    Be = Bc.clone_to("cpu")
-    sim = emu.EmuSim(S, Be)
-    leg_leg = trunk_leg = 0
-    for it in range(260):
+    sc, Bc, orc, Be, sim = scenario_pair(oracle_lib, emu, "self_collision", signature=False)
+    ctr = scenarios.KernelCounters()                     # (resync() overwrites the kernel's fault counters with the oracle's zeros)
+    for it in range(sc.substeps):
         orc.physics_substep()
         sim.physics_substep()
         for k, tol in (("root_states", 5e-4), ("dof_pos", 1e-4), ("dof_vel", 2e-2)):
             assert diff(Be, Bc, k) <= tol, (it, k, diff(Be, Bc, k))
         bad = ((Be.contact_forces - Bc.contact_forces).abs() > 5e-2 + 5e-3 * Bc.contact_forces.abs()).any(0)
         assert int(bad.sum()) == 0, (it, bad.nonzero().flatten().tolist())
-        cf = Bc.contact_forces.view(17, 3, N)
-        calf = cf[[3, 7, 11, 15]].norm(dim=1) > 0.5
-        leg_leg += int((calf.sum(0) >= 2).sum())
-        trunk_leg += int(((cf[0].norm(dim=0) > 0.5) & (calf.sum(0) >= 1)).sum())
+        sc.events.substep(Bc)
+        ctr.add(Be, Bc)
         resync(Bc, Be, sim, orc)
+    print("events[self_collision]", sc.events.free_flight())
+    leg_leg, trunk_leg = sc.events.leg_leg, sc.events.trunk_leg
     assert leg_leg > 200, (leg_leg, trunk_leg)      # (the trunk pairs are evaluated too, but the Go1's lower legs cannot reach
                                                     #  the trunk's capsule within the joint limits: they never fire on either side)
-    assert int(Be.fault_counts[:10].sum()) == 0
+    assert int(ctr.faults[:10].sum()) == 0, ctr.faults.tolist()
 
 
 def test_emulated_thigh_capsules_match_oracle(oracle_lib, emu):
     """Thigh capsules in the self-collision (pairs with a thigh: types 1-3 of the pair mask) through the KERNEL code: in free
     flight the front hips roll inwards, one thigh pitched forward and one back, and the thighs scissor into each other; kernel and oracle list the same pairs
     and agree to round-off, and a pair with a thigh does fire."""
-    N = 16
-    cfg, S, meta, Bc = make_sim("train", N, extra={"domain_rand": dict(randomize_gravity=False)})
-    S.gravity[0] = S.gravity[1] = S.gravity[2] = 0.0
-    standing_state(S, Bc, z=3.0)
-    g = torch.Generator().manual_seed(7)
-    Bc.dof_pos[:] = torch.tensor([-0.3, 1.1, -1.0, 0.3, -0.5, -1.0, 0.1, 1.0, -1.5, -0.1, 1.0, -1.5]).unsqueeze(1)
-    Bc.dof_pos[[1, 4]] += torch.empty(2, N).uniform_(-0.3, 0.3, generator=g)
-    Bc.torques.zero_()
-    Bc.torques[0] = -torch.empty(N).uniform_(3.0, 8.0, generator=g)
-    Bc.torques[3] = torch.empty(N).uniform_(3.0, 8.0, generator=g)
-    Bc.torques[1] = -torch.empty(N).uniform_(0.5, 2.5, generator=g)
-    Bc.torques[4] = torch.empty(N).uniform_(0.5, 2.5, generator=g)
-    Bc.enable_contact_signature()
-    orc = oracle_lib.Oracle(S, Bc)
-    Be = Bc.clone_to("cpu")
-    sim = emu.EmuSim(S, Be)
-    thigh_pairs = 0
-    for it in range(120):
+    sc, Bc, orc, Be, sim = scenario_pair(oracle_lib, emu, "thigh_capsules")
+    ctr = scenarios.KernelCounters()                     # (resync() overwrites the kernel's fault counters with the oracle's zeros)
+    for it in range(sc.substeps):
         orc.physics_substep()
         sim.physics_substep()
         assert torch.equal(Be.contact_signature[:3], Bc.contact_signature[:3]), it
         for k, tol in (("root_states", 5e-4), ("dof_pos", 1e-4), ("dof_vel", 2e-2)):
             assert diff(Be, Bc, k) <= tol, (it, k, diff(Be, Bc, k))
         assert not bool(((Be.contact_forces - Bc.contact_forces).abs() > 5e-2 + 5e-3 * Bc.contact_forces.abs()).any()), it
-        thigh_pairs += sum(any(c in (2, 3, 4) for c in self_pair_codes(w)[0]) for w in Bc.contact_signature[2].tolist())
+        sc.events.substep(Bc)
+        ctr.add(Be, Bc)
         resync(Bc, Be, sim, orc)
-    assert thigh_pairs > 50, thigh_pairs
-    assert int(Be.fault_counts[:10].sum()) == 0
+    print("events[thigh_capsules]", sc.events.free_flight())
+    assert sc.events.thigh_pairs > 50, sc.events.thigh_pairs
+    assert int(ctr.faults[:10].sum()) == 0, ctr.faults.tolist()
 
 
 def test_emulated_hip_capsules_match_oracle(oracle_lib, emu):
@@ -359,27 +336,11 @@ def test_emulated_hip_capsules_match_oracle(oracle_lib, emu):
     free flight a fore lower leg (knee stretched) is swung back into the hind hip of its side (environments 0-7: left side, the lower-numbered
     leg carries the lower leg = type 5; environments 8-15: the hind lower leg swung FORWARD into the fore hip = type 4), every joint held by
     a PD torque; kernel and oracle list the same pairs and agree to round-off on every substep, and both types do fire."""
-    N = 16
-    cfg, S, meta, Bc = make_sim("train", N, extra={"domain_rand": dict(randomize_gravity=False)})
-    S.gravity[0] = S.gravity[1] = S.gravity[2] = 0.0
-    standing_state(S, Bc, z=3.0)
-    g = torch.Generator().manual_seed(9)
-    back = torch.tensor([-0.4, 1.5, -0.98, -0.1, 0.8, -1.5, -0.43, 2.3, -2.5, -0.1, 1.0, -1.5])       # FL lower leg -> RL hip (tests/test_oracle_physics.py)
-    fwd = torch.tensor([0.3, 0.0, -1.5, -0.1, 0.8, -1.5, 0.58, -0.4, -1.0, -0.1, 1.0, -1.5])          # RL lower leg -> FL hip (thigh angle < 0: forward)
-    Bc.dof_pos[:, :8] = back.unsqueeze(1)
-    Bc.dof_pos[:, 8:] = fwd.unsqueeze(1)
-    Bc.dof_pos[[0, 6]] += torch.empty(2, N).uniform_(-0.15, 0.15, generator=g)
-    q_hold = Bc.dof_pos.clone()
-    drive = torch.empty(N).uniform_(1.0, 2.5, generator=g)
-    Bc.enable_contact_signature()
-    orc = oracle_lib.Oracle(S, Bc)
-    Be = Bc.clone_to("cpu")
-    sim = emu.EmuSim(S, Be)
-    seen = {5: 0, 6: 0}
-    for it in range(120):
-        tau = 30.0 * (q_hold - Bc.dof_pos) - 1.0 * Bc.dof_vel
-        tau[1, :8] = drive[:8] - 0.5 * Bc.dof_vel[1, :8]           # FL thigh backwards
-        tau[7, 8:] = -drive[8:] - 0.5 * Bc.dof_vel[7, 8:]          # RL thigh forwards
+    sc, Bc, orc, Be, sim = scenario_pair(oracle_lib, emu, "hip_capsules")
+    N = sc.N
+    ctr = scenarios.KernelCounters()                     # (resync() overwrites the kernel's fault counters with the oracle's zeros)
+    for it in range(sc.substeps):
+        tau = sc.torque_fn(Bc)
         Bc.torques.copy_(tau)
         Be.torques.copy_(tau)
         orc.physics_substep()
@@ -388,15 +349,15 @@ def test_emulated_hip_capsules_match_oracle(oracle_lib, emu):
         for k, tol in (("root_states", 5e-4), ("dof_pos", 1e-4), ("dof_vel", 2e-2)):
             assert diff(Be, Bc, k) <= tol, (it, k, diff(Be, Bc, k))
         assert not bool(((Be.contact_forces - Bc.contact_forces).abs() > 5e-2 + 5e-3 * Bc.contact_forces.abs()).any()), it
-        for w in Bc.contact_signature[2].tolist():
-            c = self_pair_codes(w)[0][1]                           # pair (0, 2): FL - RL
-            if c in seen:
-                seen[c] += 1
+        sc.events.substep(Bc)
+        ctr.add(Be, Bc)
         resync(Bc, Be, sim, orc)
+    print("events[hip_capsules]", sc.events.free_flight())
+    seen = sc.events.seen
     assert seen[5] > 50 and seen[6] > 50, seen
     hipf = Bc.contact_forces.view(17, 3, N)[[1, 9]].norm(dim=1)   # FL hip, RL hip: the forces are booked on the hip bodies
     assert float(hipf.max()) > 1.0
-    assert int(Be.fault_counts[:10].sum()) == 0
+    assert int(ctr.faults[:10].sum()) == 0, ctr.faults.tolist()
 
 
 def test_emulated_train_eval_split_matches_oracle(oracle_lib, emu):
@@ -471,44 +432,29 @@ def test_emulated_full_step_in_the_contact_heavy_regime(oracle_lib, emu, seed):
     environment leaves the tolerances unless its listed contact set differs (contact signature)."""
     N = 32
     S, Bc, orc, Be, sim = pair(oracle_lib, emu, "train", N, extra={"domain_rand": dict(randomize_gravity=False)}, signature=True)
-    g = torch.Generator().manual_seed(seed)
-    q = torch.randn(4, N, generator=g)
-    Bc.root_states[3:7] = q / q.norm(dim=0, keepdim=True)
-    Bc.root_states[2].uniform_(0.06, 0.25, generator=g)
-    Bc.root_states[7:13].uniform_(-1.5, 1.5, generator=g)
-    lo = torch.tensor([-0.86, -0.68, -2.81] * 4).unsqueeze(1)
-    hi = torch.tensor([0.86, 4.50, -0.89] * 4).unsqueeze(1)
-    Bc.dof_pos[:] = lo + (hi - lo) * torch.rand(12, N, generator=g)
-    Bc.dof_vel.uniform_(-4, 4, generator=g)
-    Bc.episode_length_buf[:] = 5
+    rng = scenarios.contact_heavy_state(Bc, seed)
     resync(Bc, Be, sim, orc)
     sh = Shadow32(oracle_lib, S, Bc, orc)
-    rng = np.random.default_rng(seed + 1)
-    peak_listed, self_pairs, split_substeps = 0, 0, 0
-    # (a full step = 4 substeps without re-synchronisation, joints at their 28 rad/s rate limits: a rate error inside its own
-    #  tolerance moves a joint by 5e-5 rad per substep)
-    tols = (("root_states", 1e-3, 1e-3), ("dof_pos", 2e-4, 0), ("dof_vel", 1e-2, 1e-3), ("torques", 5e-3, 0), ("rew_buf", 1e-4, 0), ("contact_forces", 1e-1, 5e-3))
-    for step in range(6):
-        a = (rng.standard_normal((N, 12)) * 1.5).astype(np.float32)
+    ev = scenarios.Events()
+    ctr = scenarios.KernelCounters()                     # (resync() overwrites the kernel's counters with the oracle's)
+    tols = scenarios.CONTACT_HEAVY_TOL
+    for step in range(scenarios.CONTACT_HEAVY_STEPS):
+        a = scenarios.contact_heavy_actions(rng, N)
         orc.step(a)
         sh.o.step(a)
         sim.step(torch.from_numpy(a))
         assert torch.equal(Be.reset_buf, Bc.reset_buf), step
         assert_attributed(Be, Bc, sh.B, tols, N, step)
-        sig = Bc.contact_signature.view(4, 4, N).numpy().astype(np.uint32)
-        listed = np.array([[bin(int(sig[sb, 0, e])).count("1") + bin(int(sig[sb, 1, e]) & 0x7FFFFFFF).count("1") + self_contacts_listed(sig[sb, 2, e])
-                            for e in range(N)] for sb in range(4)])
-        peak_listed = max(peak_listed, int(listed.max()))
-        self_pairs += int((sig[:, 2] & 0xFFFFFFF != 0).sum())
-        # legs holding hip / thigh rows (word 0 bits 20..27: thigh ends, word 1 bits 9..12: thigh walls, 13..20: hip ends): with two or more
-        # of them the leg phase of the sweep splits the base (csrc/go1_physics.h "MASS SPLITTING")
-        legs_split = sum((((sig[:, 0] >> (20 + 2 * leg)) & 3) | ((sig[:, 1] >> (13 + 2 * leg)) & 3) | ((sig[:, 1] >> (9 + leg)) & 1)) != 0 for leg in range(4))
-        split_substeps += int((legs_split >= 2).sum())
+        ev.full_step(Bc)
+        ctr.add(Be, Bc)
+        assert int(Be.contact_drop_counts.sum()) == int(Bc.contact_drop_counts.sum()), step      # (both started the step from the same counts)
         resync(Bc, Be, sim, orc)
         sh.sync()
+    print(f"events[contact_heavy, seed {seed}]", ev.contact_heavy())
+    peak_listed, split_substeps = ev.peak_listed, ev.split_substeps
     assert peak_listed > 8, peak_listed                               # beyond what round 2 could solve
     assert split_substeps > 50, split_substeps                        # the mass-split leg phase ran (two or more legs with hip / thigh rows)
-    assert int(Be.fault_counts[:10].sum()) == 0 and int(Be.contact_drop_counts.sum()) == int(Bc.contact_drop_counts.sum())
+    assert int(ctr.faults[:10].sum()) == 0, ctr.faults.tolist()
 
 
 @pytest.mark.parametrize("walls,above", [(False, False), (True, False), (False, True)])

@@ -181,6 +181,15 @@ class ProductPair:
     def step(self, a):
         self.sim.step(a)
         self.sim_t.step(a)
+        return self._compare()
+
+    def substep(self):
+        """one physics substep of both (mode 2 of the step kernel) from the buffers as they are"""
+        self.sim.physics_substep()
+        self.sim_t.physics_substep()
+        return self._compare()
+
+    def _compare(self):
         torch.cuda.synchronize()
         same = identical_envs(self.Bg, self.Bt, self.Bc.root_states.shape[1], self.keys, self.by_key)
         self.env_steps += same.numel()
