@@ -229,6 +229,67 @@
  *   environments with group[k] == g.  Row m is the metric row of go1eval_reduce over accumulators that folded the one value
  *   values[m][k], exactly as go1eval_response_reduce forms its rows (a NaN counts in nonfinite).  The last row of a group
  *   (index = Go1RecoveryGroupField): traced environments, environments with status 0, 1, 2, 3, then 0 (sums in the same fixed order).
+ *
+ * ---- terrain traversal (fifth kernel family; index = Go1TerrainMetric) -------------------------------------------------------------
+ * The four families above measure on flat ground.  This one measures a policy on the tile grid of a generated terrain: whether a
+ * robot LEAVES THE TILE it was placed on (the criterion of legged_gym-style terrain curricula), falls or times out first, how
+ * far it gets, and, while it is under way, how high its base and its feet are ABOVE THE GROUND THEY ARE OVER, how often a foot
+ * is pushed sideways and how often a penalised body touches something.  Accumulators, folding rule and reduction are the tables'.
+ *
+ * Height sample h(x, y): the simulator's own convention for "the ground under a point" (the reference's _get_heights), NOT the
+ * bilinear contact surface and not the vertical walls of a trimesh terrain.  Every operation is an fp32 operation:
+ *   x or y not finite: h = NaN, tested first: nothing below is evaluated for such a point.
+ *   qx = (x + hf_border) / hf_hscale (one add, one division);  px = 0 if not qx > 0, hf_rows - 2 if qx > (float)(hf_rows - 2), else
+ *   (long)qx: the truncated index clamped to [0, hf_rows - 2].  The clamp is applied in fp32 BEFORE the conversion: the result
+ *   is that of converting first for every qx a long can hold, and no value outside that range is ever converted.
+ *   py likewise from y and hf_cols.  h = (float)min(s[px][py], s[px + 1][py], s[px][py + 1]) * hf_vscale: the minimum of three
+ *   int16 samples of height_samples ([hf_rows][hf_cols], row-major), converted to fp32, one multiply.  height_samples == NULL: h = 0
+ *   for finite x, y (the plane).
+ *
+ * A foot f is as in the behaviour table (body 4 + 4 f of contact_forces, rows 3 f .. 3 f + 2 of foot_positions); (F_x, F_y, F_z)
+ * of body b are rows 3 b .. 3 b + 2 of contact_forces; cmd[k] = commands[k][e]; a_f = z_f - h(x_f, y_f) (one subtraction) is the
+ * height of foot f above the ground under it.  Five per-step metrics (fp32; a sum over the feet adds its fp32 terms in an fp64
+ * carry, feet in ascending order, and rounds to fp32 once; there is no rounding freedom: same inputs, same bits):
+ *   base_height_terrain     root_states[2] - h(root_states[0], root_states[1])
+ *   feet_clearance_terrain  sum over the feet of ((cmd[9] * ph + 0.02) - a_f)^2 * (1 - desired_contact_states[f]), ph as in the
+ *                           behaviour table's feet_clearance: that expression with z_f replaced by a_f
+ *   swing_foot_height       the mean over the feet with desired_contact_states[f] <= 0.5 of a_f - GO1EVAL_FOOT_RADIUS: the fp32
+ *                           terms in an fp64 carry, divided by the number of such feet in fp64, rounded to fp32 once.  No such
+ *                           foot: NOTHING is folded for this metric on this step (neither count nor nonfinite moves).
+ *   stumble                 1 if some foot has sqrtf(F_x * F_x + F_y * F_y) > 5.0f * fabsf(F_z), else 0: legged_gym's feet-stumble
+ *                           criterion, a foot pushed sideways by a riser.  The REFERENCE HAS NO SUCH TERM.
+ *   collision               the number of bodies b in [0, 17) with bit b set in penalised_body_mask and
+ *                           sqrtf((F_x * F_x + F_y * F_y) + F_z * F_z) > 0.1f, as a float (the reference's _reward_collision).  Bits
+ *                           17 .. 31 of the mask are ignored.
+ *
+ * Per environment the family carries status (Go1TerrainStatus), steps, end_step and max_dist.  An environment is measured for
+ * its FIRST EPISODE ON ITS HOME TILE only: once its status is not RUNNING no later launch reads or writes anything of it.
+ * go1eval_terrain_accumulate, per environment e (one thread each, no atomics, no LDS; every word has one writer), in this order:
+ *   1. status[e] != RUNNING: return.
+ *   2. reset_buf[e] != 0: status[e] = TIMED_OUT if time_out_buf[e] != 0, else FELL; end_step[e] = steps[e] + 1.  Nothing else: the
+ *      buffers already hold the new episode's pose (steps and max_dist stay as the last measured step left them).
+ *   3. steps[e] += 1.  dx = root_states[0] - env_origins[0], dy = root_states[1] - env_origins[1] (fp32);
+ *      max_dist[e] = fmaxf(max_dist[e], sqrtf(dx * dx + dy * dy)).  If fabsf(dx) > tile_length / 2 or fabsf(dy) > tile_width / 2:
+ *      status[e] = TRAVERSED, end_step[e] = steps[e], and nothing is folded.  The comparison is strict (a robot exactly on the edge
+ *      is still on its tile), and a dx or dy that is not finite does not traverse: both are tested for finiteness first (a NaN
+ *      would fail the comparisons by itself, an infinity would not; fmaxf drops a NaN and keeps an infinity in max_dist).
+ *   4. episode_length_buf[e] <= warmup_steps: nothing more.
+ *   5. the five per-step metrics are folded in the order of Go1TerrainMetric by the folding rule of go1eval_accumulate: a
+ *      non-finite value counts in nonfinite and enters nothing else.
+ * go1eval_terrain_clear: accumulators as go1eval_clear; status = RUNNING, steps = 0, end_step = 0, max_dist = 0.
+ * go1eval_terrain_reduce: results[num_groups][GO1EVAL_NUM_TERRAIN + GO1EVAL_NUM_OUTCOME + 1][GO1EVAL_NUM_FIELDS].
+ *   Rows 0 .. 4: the metric rows of go1eval_reduce (the same device function, the same fixed combination order).
+ *   Rows 5 .. 8 (index = GO1EVAL_NUM_TERRAIN + Go1TerrainOutcome): the metric row over accumulators that folded ONE fp32 value per
+ *   environment, exactly as go1eval_recovery_reduce forms its rows (a NaN counts in nonfinite):
+ *     traversed   1 if TRAVERSED, 0 if FELL or TIMED_OUT, NaN while RUNNING (the window was too short to decide)
+ *     fell        1 if FELL, 0 if TRAVERSED or TIMED_OUT, NaN while RUNNING
+ *     distance    max_dist[e]: the largest planar distance from the tile's origin over the measured steps
+ *     end_time    (float)end_step[e] * dt (one fp32 multiply), NaN while RUNNING
+ *   Row 9 (index = Go1TerrainGroupField): environments, environments with status 0, 1, 2, 3 (sums in the same fixed order), then
+ *   success_rate = traversed / (traversed + fell + timed_out), one fp64 division, NaN when the denominator is 0.
+ * Refused before any launch: -1 no config, no buffers or num_envs <= 0;  -2 an accumulator or a state array is missing;  -3 an
+ *   input is missing (height_samples may be NULL);  -5 no group, no table or num_groups <= 0;  -12 the geometry: hf_rows < 2 or
+ *   hf_cols < 2 with a height field, hf_hscale <= 0, tile_length <= 0, tile_width <= 0 or dt <= 0 (a NaN is refused as well).
  */
 #ifndef GO1EVAL_H_INCLUDED
 #define GO1EVAL_H_INCLUDED
@@ -503,6 +564,80 @@ int go1eval_recovery(const Go1RecoveryConfig* cfg, const Go1RecoveryBuffers* buf
 
 /* the recovery table from values and status (which it leaves as they are).  One launch.  No group, no table or no groups: -5. */
 int go1eval_recovery_reduce(const Go1RecoveryConfig* cfg, const Go1RecoveryBuffers* buf, void* stream);
+
+/* ---- terrain traversal ------------------------------------------------------------------------------------------------------------ */
+#define GO1EVAL_NUM_TERRAIN 5
+#define GO1EVAL_NUM_OUTCOME 4
+#define GO1EVAL_STUMBLE_RATIO 5.0    /* a foot stumbles when its horizontal contact force exceeds this many times its vertical one (legged_gym) */
+#define GO1EVAL_COLLISION_FORCE 0.1  /* N: a penalised body collides when its contact force exceeds this (the reference's _reward_collision) */
+
+enum Go1TerrainMetric {
+  GO1TERRAIN_BASE_HEIGHT_TERRAIN = 0, GO1TERRAIN_FEET_CLEARANCE_TERRAIN = 1, GO1TERRAIN_SWING_FOOT_HEIGHT = 2, GO1TERRAIN_STUMBLE = 3,
+  GO1TERRAIN_COLLISION = 4
+};
+enum Go1TerrainStatus { GO1TERRAIN_S_RUNNING = 0, GO1TERRAIN_S_TRAVERSED = 1, GO1TERRAIN_S_FELL = 2, GO1TERRAIN_S_TIMED_OUT = 3 };
+/* rows GO1EVAL_NUM_TERRAIN + Go1TerrainOutcome of the terrain table */
+enum Go1TerrainOutcome { GO1TERRAIN_O_TRAVERSED = 0, GO1TERRAIN_O_FELL = 1, GO1TERRAIN_O_DISTANCE = 2, GO1TERRAIN_O_END_TIME = 3 };
+/* columns of a group's own row (row GO1EVAL_NUM_TERRAIN + GO1EVAL_NUM_OUTCOME) of the terrain table */
+enum Go1TerrainGroupField {
+  GO1TERRAIN_G_ENVS = 0, GO1TERRAIN_G_RUNNING = 1, GO1TERRAIN_G_TRAVERSED = 2, GO1TERRAIN_G_FELL = 3, GO1TERRAIN_G_TIMED_OUT = 4,
+  GO1TERRAIN_G_SUCCESS_RATE = 5
+};
+
+typedef struct Go1TerrainConfig {
+  int32_t num_envs;              /* N of the simulator's SoA buffers */
+  int32_t warmup_steps;          /* steps with episode_length_buf <= warmup_steps fold no metric (status and distance still advance) */
+  int32_t num_groups;            /* G of the result table */
+  int32_t hf_rows;               /* the height field's samples along x (ignored when height_samples is NULL) */
+  int32_t hf_cols;               /* and along y */
+  uint32_t penalised_body_mask;  /* bit b: body b counts towards `collision` */
+  float dt;                      /* s, the policy step: end_time = end_step * dt */
+  float hf_hscale;               /* m per sample along x and y */
+  float hf_vscale;               /* m per int16 unit */
+  float hf_border;               /* m: the field starts at world (-hf_border, -hf_border) */
+  float tile_length;             /* m: a tile's extent along x */
+  float tile_width;              /* m: and along y */
+} Go1TerrainConfig;
+
+typedef struct Go1TerrainBuffers {
+  /* read by go1eval_terrain_accumulate */
+  const float* root_states;             /* [13][N]; rows 0..2 are read */
+  const float* commands;                /* [>= 10][N]; row 9 is read */
+  const float* contact_forces;          /* [17 * 3][N] */
+  const float* foot_positions;          /* [4 * 3][N], world frame */
+  const float* desired_contact_states;  /* [4][N] */
+  const float* foot_indices;            /* [4][N] */
+  const float* env_origins;             /* [3][N]; rows 0, 1: the centre of the environment's home tile */
+  const int16_t* height_samples;        /* [hf_rows][hf_cols] or NULL (the plane: the ground is 0) */
+  const uint8_t* reset_buf;             /* [N] */
+  const uint8_t* time_out_buf;          /* [N] */
+  const int32_t* episode_length_buf;    /* [N] */
+  /* accumulators, [GO1EVAL_NUM_TERRAIN][N] */
+  uint32_t* count;
+  double* sum;
+  double* sumsq;
+  float* min;
+  float* max;
+  uint32_t* nonfinite;
+  /* per-environment state, [N] */
+  uint8_t* status;                      /* Go1TerrainStatus */
+  uint32_t* steps;                      /* measured steps */
+  uint32_t* end_step;                   /* the step at which the status left RUNNING (1 = the first step after the clear) */
+  float* max_dist;                      /* m */
+  /* go1eval_terrain_reduce */
+  const int32_t* group;                 /* [N] */
+  double* results;                      /* [num_groups][GO1EVAL_NUM_TERRAIN + GO1EVAL_NUM_OUTCOME + 1][GO1EVAL_NUM_FIELDS] */
+} Go1TerrainBuffers;
+
+/* empty accumulators, every environment RUNNING at step 0.  One launch. */
+int go1eval_terrain_clear(const Go1TerrainConfig* cfg, const Go1TerrainBuffers* buf, void* stream);
+
+/* after a simulator step: advance every RUNNING environment and fold its step.  One launch, one thread per environment.
+ * Geometry refused: -12. */
+int go1eval_terrain_accumulate(const Go1TerrainConfig* cfg, const Go1TerrainBuffers* buf, void* stream);
+
+/* at the end: the result table from the accumulators and the state (which it leaves as they are).  One launch.  dt <= 0: -12. */
+int go1eval_terrain_reduce(const Go1TerrainConfig* cfg, const Go1TerrainBuffers* buf, void* stream);
 
 /* "go1eval <version> (gfx950) go1-src:<16 hex digits of the source hash>" */
 const char* go1eval_version(void);

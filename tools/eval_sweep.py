@@ -28,6 +28,15 @@ With `--push` every environment trots at 1 m/s and is pushed once with one cell 
 and analysed on the device (go1_gym_learn.eval_metrics.recovery), `<out>/eval/<preset>_push.json` is written and the recovery table
 is printed and appended to `<out>/eval/<preset>_push.md`.  `--trace-envs I [I ...]` also writes `<preset>_push_trace.npz` and the
 figure of each to `<preset>_push_trace_env<I>.png`.
+
+    python tools/eval_sweep.py --checkpoint RUN_DIR/checkpoints --out RUN_DIR --terrain --rows 4 --cols 5 --vx 1.0 --window 500
+
+With a bare `--terrain` every environment is placed on one tile of a curriculum grid of `--rows` difficulties x `--cols` terrain
+types (`--mesh trimesh | heightfield`, `--proportions P ...` for the mix of types), commanded `--vx` m/s forward, and measured for `--window` steps on the device
+(go1_gym_learn.eval_metrics.terrain): did it leave its tile, fall or time out, how often did it stumble, how high did its feet
+swing above the ground.  `<out>/eval/<preset>_terrain.json` is written and the grid (rows = difficulty, columns = terrain type) is
+printed and appended to `<out>/eval/<preset>_terrain.md`.  (`--terrain MESH` with a value keeps its meaning for the other sweeps:
+the mesh type of their terrain.)
 Run on the GPU box."""
 import argparse
 import json
@@ -90,14 +99,21 @@ def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--checkpoint", required=True)
     ap.add_argument("--presets", nargs="+", default=["static_medium", "rand_large"], choices=sorted(DR_SETTINGS))
-    ap.add_argument("--vx", nargs="+", type=float, default=[0.5, 1.0, 1.5])
+    ap.add_argument("--vx", nargs="+", type=float, default=None, help="default: 0.5 1.0 1.5; with a bare --terrain one value, default 1.0")
     ap.add_argument("--yaw", nargs="+", type=float, default=[0.0])
     ap.add_argument("--gaits", nargs="+", default=["trotting"], choices=sorted(sweep.GAITS))
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup-steps", type=int, default=25)
     ap.add_argument("--seed", type=int, default=1)
-    ap.add_argument("--terrain", default=None, choices=["plane", "heightfield", "trimesh"])
+    ap.add_argument("--terrain", nargs="?", default=None, const="tiles", choices=["plane", "heightfield", "trimesh", "tiles"],
+                    help="with a value: the mesh type of the sweep's terrain; bare: the terrain-traversal sweep over a tile grid")
+    ap.add_argument("--rows", type=int, default=None, help="with a bare --terrain: difficulties (tile rows) of the grid, default 4")
+    ap.add_argument("--cols", type=int, default=None, help="with a bare --terrain: terrain types (tile columns) of the grid, default 5")
+    ap.add_argument("--window", type=int, default=None, help="with a bare --terrain: measured steps, default 500")
+    ap.add_argument("--mesh", default=None, choices=["heightfield", "trimesh"], help="with a bare --terrain: the mesh type, default trimesh")
+    ap.add_argument("--proportions", nargs="+", type=float, default=None,
+                    help="with a bare --terrain: terrain_proportions of the grid (default: slopes, rough slopes, stairs down, stairs up, obstacles)")
     ap.add_argument("--behaviour", action="store_true", help="measure gait and behaviour tracking over the --axis product instead of the velocity grid")
     ap.add_argument("--axis", nargs="+", action="append", metavar=("NAME", "VALUE"), help="a behaviour command and its values; repeatable")
     ap.add_argument("--response", action="store_true", help="measure the step response to the --switch of one command instead of the velocity grid")
@@ -109,6 +125,21 @@ def parse_args(argv=None):
                     help="with --push: directions in degrees in the robot's heading frame (0 a shove from behind, 90 a push to the left)")
     ap.add_argument("--out", required=True)
     a = ap.parse_args(argv)
+    a.tiles = a.terrain == "tiles"
+    if not a.tiles and any(v is not None for v in (a.rows, a.cols, a.window, a.mesh, a.proportions)):
+        ap.error("--rows, --cols, --window, --mesh and --proportions need a bare --terrain")
+    if a.tiles:
+        if a.response or a.behaviour or a.push:
+            ap.error("a bare --terrain excludes --response, --behaviour and --push")
+        if a.vx is not None and len(a.vx) != 1:
+            ap.error("a bare --terrain takes one --vx")
+        a.terrain = None
+        a.rows, a.cols, a.window = (d if v is None else v for v, d in ((a.rows, 4), (a.cols, 5), (a.window, 500)))
+        a.mesh = a.mesh or "trimesh"
+        a.vx = a.vx or [1.0]
+        if a.rows < 1 or a.cols < 1 or a.window < 1:
+            ap.error("--rows, --cols and --window have to be at least 1")
+    a.vx = a.vx or [0.5, 1.0, 1.5]
     if a.switch and not a.response:
         ap.error("--switch needs --response")
     if a.trace_envs and not (a.response or a.push):
@@ -175,6 +206,21 @@ def run_push(a, policy):
                 response.plot_trace(res["trace"], e, f"{stem}_push_trace_env{e}.png", dt=res["dt"])
 
 
+def run_terrain(a, policy):
+    from go1_gym_learn.eval_metrics import terrain
+    for preset in a.presets:
+        res = terrain.run_terrain_sweep(policy, preset, vx=a.vx[0], num_envs=a.envs, window=a.window, warmup=a.warmup_steps, seed=a.seed,
+                                        num_rows=a.rows, num_cols=a.cols, mesh_type=a.mesh, terrain_proportions=a.proportions)
+        stem = os.path.join(a.out, "eval", preset)
+        with open(stem + "_terrain.json", "w") as f:
+            json.dump(terrain.terrain_to_json(res), f, indent=1)
+        text = f"### {preset}: {a.envs} environments on {a.rows} x {a.cols} {a.mesh} tiles, {a.vx[0]} m/s forward, {a.window} steps, terrain traversal\n\n"
+        text += "success rate / stumble rate / mean swing foot height [m] / fall rate\n\n" + terrain.terrain_markdown_grid(res) + "\n"
+        print(text)
+        with open(stem + "_terrain.md", "a") as f:
+            f.write(text + "\n")
+
+
 def behaviour_axes(a):
     """{command name: [values]} of the --axis options, in the order given"""
     from go1_gym_learn.eval_metrics.behaviour import COMMAND_INDEX
@@ -199,6 +245,8 @@ def main(argv=None):
         return run_response(a, policy)
     if a.push:
         return run_push(a, policy)
+    if a.tiles:
+        return run_terrain(a, policy)
     if a.behaviour:
         from go1_gym_learn.eval_metrics import behaviour
         axes = behaviour_axes(a)

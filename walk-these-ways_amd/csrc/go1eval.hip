@@ -15,6 +15,10 @@
 // push_kernel / recovery_kernel / recovery_reduce_kernel: the push and the disturbance recovery: one thread per pushed environment
 // that adds a velocity step to its rows of root_states, and the response's shapes for the analysis of the trace that follows
 // (the same loads, the same reduction through reduce_metric_row and status_row).  tests/recovery_ref.py is the model.
+// terrain_accumulate_kernel / terrain_reduce_kernel: terrain traversal, the tables' shapes once more: one thread per environment
+// that carries its status, step count and distance ([N], one writer per word) and reads fifteen int16 samples of the height field
+// under its base and feet, the family's only scattered loads, issued as one batch; the reduction goes through reduce_metric_row
+// (metric rows, and outcome rows over one computed value per environment) and status_row.  tests/terrain_ref.py is the model.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -428,12 +432,13 @@ struct FoldedOnce {
 
 // the last row of a group of the response and recovery tables, by one workgroup of RT threads in reduce_metric_row's combination
 // order: traced environments, environments with status 0, 1, 2, 3, then 0 (the response knows no status 3: its count is 0)
-__device__ __forceinline__ void status_row(const int32_t* status, const int32_t* group, int g, int K, double (*lds)[RT], double* out) {
+template <class Status>
+__device__ __forceinline__ void status_row(const Status* status, const int32_t* group, int g, int K, double (*lds)[RT], double* out) {
   const int t = (int)threadIdx.x;
   double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = 0.0;
   for (int e = t; e < K; e += RT) {
     if (group[e] != g) continue;
-    const int st = status[e];
+    const int st = (int)status[e];
     a0 += 1.0; a1 += st == 0 ? 1.0 : 0.0; a2 += st == 1 ? 1.0 : 0.0; a3 += st == 2 ? 1.0 : 0.0; a4 += st == 3 ? 1.0 : 0.0;
   }
   lds[0][t] = a0; lds[1][t] = a1; lds[2][t] = a2; lds[3][t] = a3; lds[4][t] = a4;
@@ -574,6 +579,156 @@ extern "C" __global__ void __launch_bounds__(RT) recovery_reduce_kernel(const Re
     return;
   }
   status_row(b.status, b.group, g, K, lds, out);
+}
+
+// ---- terrain traversal ----------------------------------------------------------------------------------------------------------
+constexpr int NTM = GO1EVAL_NUM_TERRAIN, NTO = GO1EVAL_NUM_OUTCOME;
+
+struct TerrainArgs {
+  Go1TerrainConfig c;
+  Go1TerrainBuffers b;
+};
+
+namespace {
+// where the three samples under world (x, y) start: the truncated index, clamped in fp32 before the conversion (see the header).
+// ok = false for a point that is not finite: its offset is 0 (in bounds, never used) and nothing of it is converted.
+struct Cell { long at; bool ok; };
+__device__ __forceinline__ long cell_index(float v, float border, float hscale, int samples) {
+  const float q = (v + border) / hscale, last = (float)(samples - 2);
+  return q > last ? (long)(samples - 2) : (q > 0.0f ? (long)q : 0L);
+}
+__device__ __forceinline__ Cell cell_under(const Go1TerrainConfig& c, bool field, float x, float y) {
+  if (!(isfinite(x) && isfinite(y))) return {0L, false};
+  if (!field) return {0L, true};                                 // the plane: no sample is read
+  return {cell_index(x, c.hf_border, c.hf_hscale, c.hf_rows) * c.hf_cols + cell_index(y, c.hf_border, c.hf_hscale, c.hf_cols), true};
+}
+
+// one fp32 value per environment seen as the accumulators of an environment that folded it once (FoldedOnce, over a computed value)
+struct TerrainOutcome {
+  const uint8_t* status; const uint32_t* end_step; const float* max_dist; float dt; int which;
+  __device__ float operator()(size_t e) const {
+    const int st = status[e];
+    switch (which) {
+      case GO1TERRAIN_O_TRAVERSED: return st == GO1TERRAIN_S_RUNNING ? NAN : (st == GO1TERRAIN_S_TRAVERSED ? 1.0f : 0.0f);
+      case GO1TERRAIN_O_FELL: return st == GO1TERRAIN_S_RUNNING ? NAN : (st == GO1TERRAIN_S_FELL ? 1.0f : 0.0f);
+      case GO1TERRAIN_O_DISTANCE: return max_dist[e];
+      default: return st == GO1TERRAIN_S_RUNNING ? NAN : (float)end_step[e] * dt;
+    }
+  }
+};
+struct OutcomeOnce {
+  struct Count { TerrainOutcome v; __device__ uint32_t operator[](size_t i) const { return isfinite(v(i)) ? 1u : 0u; } };
+  struct Nonfinite { TerrainOutcome v; __device__ uint32_t operator[](size_t i) const { return isfinite(v(i)) ? 0u : 1u; } };
+  struct Sum { TerrainOutcome v; __device__ double operator[](size_t i) const { const float x = v(i); return isfinite(x) ? (double)x : 0.0; } };
+  struct Sumsq { TerrainOutcome v; __device__ double operator[](size_t i) const { const float x = v(i); return isfinite(x) ? (double)x * (double)x : 0.0; } };
+  struct Value { TerrainOutcome v; __device__ float operator[](size_t i) const { return v(i); } };
+  const int32_t* group;
+  Count count; Nonfinite nonfinite; Sum sum; Sumsq sumsq; Value min, max;
+};
+}  // namespace
+
+extern "C" __global__ void __launch_bounds__(ACC_THREADS) terrain_clear_kernel(const TerrainArgs A) {
+  const int N = A.c.num_envs;
+  const int e = (int)(blockIdx.x * ACC_THREADS + threadIdx.x);
+  if (e >= N) return;
+  const Go1TerrainBuffers& b = A.b;
+  for (int m = 0; m < NTM; m++) {
+    const size_t i = (size_t)m * N + e;
+    b.count[i] = 0u; b.nonfinite[i] = 0u; b.sum[i] = 0.0; b.sumsq[i] = 0.0; b.min[i] = INFINITY; b.max[i] = -INFINITY;
+  }
+  b.status[e] = GO1TERRAIN_S_RUNNING; b.steps[e] = 0u; b.end_step[e] = 0u; b.max_dist[e] = 0.0f;
+}
+
+extern "C" __global__ void __launch_bounds__(ACC_THREADS) terrain_accumulate_kernel(const TerrainArgs A) {
+  const Go1TerrainConfig& c = A.c;
+  const int N = c.num_envs;
+  const int e = (int)(blockIdx.x * ACC_THREADS + threadIdx.x);
+  if (e >= N) return;
+  const Go1TerrainBuffers& b = A.b;
+  if (b.status[e] != GO1TERRAIN_S_RUNNING) return;
+  if (b.reset_buf[e]) {                                          // the episode ended: the buffers hold the next one's pose
+    b.status[e] = b.time_out_buf[e] ? GO1TERRAIN_S_TIMED_OUT : GO1TERRAIN_S_FELL;
+    b.end_step[e] = b.steps[e] + 1u;
+    return;
+  }
+  const auto row = [N, e](const float* p, int k) { return p[(size_t)k * N + e]; };
+  const uint32_t steps = b.steps[e] + 1u;
+  b.steps[e] = steps;
+  const V3 base = {row(b.root_states, 0), row(b.root_states, 1), row(b.root_states, 2)};
+  const float dx = base.x - row(b.env_origins, 0), dy = base.y - row(b.env_origins, 1);
+  b.max_dist[e] = fmaxf(b.max_dist[e], sqrtf(dx * dx + dy * dy));
+  if (isfinite(dx) && isfinite(dy) && (fabsf(dx) > c.tile_length / 2 || fabsf(dy) > c.tile_width / 2)) {
+    b.status[e] = GO1TERRAIN_S_TRAVERSED; b.end_step[e] = steps;
+    return;
+  }
+  if (b.episode_length_buf[e] <= c.warmup_steps) return;
+
+  // the five points (base, four feet), then their fifteen samples: the only scattered loads, all issued before the first is used
+  V3 pos[5];
+  pos[0] = base;
+  for (int f = 0; f < 4; f++) pos[1 + f] = {row(b.foot_positions, 3 * f), row(b.foot_positions, 3 * f + 1), row(b.foot_positions, 3 * f + 2)};
+  const bool field = b.height_samples != nullptr;
+  Cell cell[5];
+  for (int p = 0; p < 5; p++) cell[p] = cell_under(c, field, pos[p].x, pos[p].y);
+  int16_t s[5][3] = {};
+  if (field) {
+    for (int p = 0; p < 5; p++) {
+      const int16_t* q = b.height_samples + cell[p].at;
+      s[p][0] = q[0]; s[p][1] = q[c.hf_cols]; s[p][2] = q[1];
+    }
+  }
+  float above[5];                                                // z minus the ground under the point
+  for (int p = 0; p < 5; p++) {
+    int16_t lowest = s[p][0] < s[p][1] ? s[p][0] : s[p][1];
+    lowest = lowest < s[p][2] ? lowest : s[p][2];
+    above[p] = pos[p].z - (cell[p].ok ? (field ? (float)lowest * c.hf_vscale : 0.0f) : NAN);
+  }
+
+  const float cmd_swing = row(b.commands, 9);
+  double clearance = 0.0, swing = 0.0;                           // (fp64 carry over fp32 terms, one rounding: see the header)
+  int swinging = 0;
+  bool stumble = false;
+  for (int f = 0; f < 4; f++) {
+    const float desired = row(b.desired_contact_states, f), index = row(b.foot_indices, f), a = above[1 + f];
+    const float swing_phase = 1.0f - fabsf(1.0f - fminf(fmaxf(index * 2.0f - 1.0f, 0.0f), 1.0f) * 2.0f);
+    const float miss = cmd_swing * swing_phase + (float)GO1EVAL_FOOT_RADIUS - a;
+    clearance += (double)(miss * miss * (1.0f - desired));
+    if (desired <= 0.5f) { swing += (double)(a - (float)GO1EVAL_FOOT_RADIUS); swinging += 1; }
+    const int body = 4 + 4 * f;
+    const float fx = row(b.contact_forces, 3 * body), fy = row(b.contact_forces, 3 * body + 1), fz = row(b.contact_forces, 3 * body + 2);
+    if (sqrtf(fx * fx + fy * fy) > (float)GO1EVAL_STUMBLE_RATIO * fabsf(fz)) stumble = true;
+  }
+  int collisions = 0;
+  for (int body = 0; body < 17; body++) {
+    if (!((c.penalised_body_mask >> body) & 1u)) continue;      // (the same branch in every lane)
+    const float fx = row(b.contact_forces, 3 * body), fy = row(b.contact_forces, 3 * body + 1), fz = row(b.contact_forces, 3 * body + 2);
+    collisions += sqrtf(fx * fx + fy * fy + fz * fz) > (float)GO1EVAL_COLLISION_FORCE ? 1 : 0;
+  }
+  fold(b, GO1TERRAIN_BASE_HEIGHT_TERRAIN, N, e, above[0]);
+  fold(b, GO1TERRAIN_FEET_CLEARANCE_TERRAIN, N, e, (float)clearance);
+  if (swinging > 0) fold(b, GO1TERRAIN_SWING_FOOT_HEIGHT, N, e, (float)(swing / (double)swinging));
+  fold(b, GO1TERRAIN_STUMBLE, N, e, stumble ? 1.0f : 0.0f);
+  fold(b, GO1TERRAIN_COLLISION, N, e, (float)collisions);
+}
+
+extern "C" __global__ void __launch_bounds__(RT) terrain_reduce_kernel(const TerrainArgs A) {
+  __shared__ double lds[NF][RT];
+  constexpr int rows = NTM + NTO + 1;
+  const int N = A.c.num_envs;
+  const int g = (int)blockIdx.x / rows, m = (int)blockIdx.x % rows;
+  const Go1TerrainBuffers& b = A.b;
+  double* out = b.results + ((size_t)g * rows + m) * NF;
+  if (m < NTM) { reduce_metric_row(b, g, m, N, lds, out); return; }
+  if (m < NTM + NTO) {
+    const TerrainOutcome v = {b.status, b.end_step, b.max_dist, A.c.dt, m - NTM};
+    const OutcomeOnce once = {b.group, {v}, {v}, {v}, {v}, {v}, {v}};
+    reduce_metric_row(once, g, 0, N, lds, out);                  // (row 0 of a table of one row: index e)
+    return;
+  }
+  status_row(b.status, b.group, g, N, lds, out);                 // environments, status 0, 1, 2, 3
+  if (threadIdx.x != 0) return;
+  const double ended = out[GO1TERRAIN_G_TRAVERSED] + out[GO1TERRAIN_G_FELL] + out[GO1TERRAIN_G_TIMED_OUT];
+  out[GO1TERRAIN_G_SUCCESS_RATE] = ended > 0.0 ? out[GO1TERRAIN_G_TRAVERSED] / ended : (double)NAN;
 }
 
 namespace {
@@ -729,6 +884,43 @@ extern "C" int go1eval_recovery_reduce(const Go1RecoveryConfig* cfg, const Go1Re
   if (cfg->num_groups <= 0 || !buf->group || !buf->results) return -5;
   const RecoveryArgs A = args_of(cfg, buf);
   hipLaunchKernelGGL(recovery_reduce_kernel, dim3((unsigned)(cfg->num_groups * (NV + 1))), dim3(RT), 0, (hipStream_t)stream, A);
+  return hipGetLastError() == hipSuccess ? 0 : -20;
+}
+
+namespace {
+int check(const Go1TerrainConfig* cfg, const Go1TerrainBuffers* buf) {
+  if (!cfg || !buf || cfg->num_envs <= 0) return -1;
+  if (!buf->count || !buf->sum || !buf->sumsq || !buf->min || !buf->max || !buf->nonfinite || !buf->status || !buf->steps || !buf->end_step ||
+      !buf->max_dist) return -2;
+  return 0;
+}
+TerrainArgs args_of(const Go1TerrainConfig* cfg, const Go1TerrainBuffers* buf) { TerrainArgs A; A.c = *cfg; A.b = *buf; return A; }
+}  // namespace
+
+extern "C" int go1eval_terrain_clear(const Go1TerrainConfig* cfg, const Go1TerrainBuffers* buf, void* stream) {
+  if (int rc = check(cfg, buf)) return rc;
+  const TerrainArgs A = args_of(cfg, buf);
+  hipLaunchKernelGGL(terrain_clear_kernel, env_grid(cfg->num_envs), dim3(ACC_THREADS), 0, (hipStream_t)stream, A);
+  return hipGetLastError() == hipSuccess ? 0 : -20;
+}
+
+extern "C" int go1eval_terrain_accumulate(const Go1TerrainConfig* cfg, const Go1TerrainBuffers* buf, void* stream) {
+  if (int rc = check(cfg, buf)) return rc;
+  if (!buf->root_states || !buf->commands || !buf->contact_forces || !buf->foot_positions || !buf->desired_contact_states ||
+      !buf->foot_indices || !buf->env_origins || !buf->reset_buf || !buf->time_out_buf || !buf->episode_length_buf) return -3;
+  if (buf->height_samples && (cfg->hf_rows < 2 || cfg->hf_cols < 2)) return -12;
+  if (!(cfg->hf_hscale > 0.0f && cfg->tile_length > 0.0f && cfg->tile_width > 0.0f && cfg->dt > 0.0f)) return -12;
+  const TerrainArgs A = args_of(cfg, buf);
+  hipLaunchKernelGGL(terrain_accumulate_kernel, env_grid(cfg->num_envs), dim3(ACC_THREADS), 0, (hipStream_t)stream, A);
+  return hipGetLastError() == hipSuccess ? 0 : -20;
+}
+
+extern "C" int go1eval_terrain_reduce(const Go1TerrainConfig* cfg, const Go1TerrainBuffers* buf, void* stream) {
+  if (int rc = check(cfg, buf)) return rc;
+  if (cfg->num_groups <= 0 || !buf->group || !buf->results) return -5;
+  if (!(cfg->dt > 0.0f)) return -12;
+  const TerrainArgs A = args_of(cfg, buf);
+  hipLaunchKernelGGL(terrain_reduce_kernel, dim3((unsigned)(cfg->num_groups * (NTM + NTO + 1))), dim3(RT), 0, (hipStream_t)stream, A);
   return hipGetLastError() == hipSuccess ? 0 : -20;
 }
 

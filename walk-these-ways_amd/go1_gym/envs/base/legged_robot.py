@@ -151,6 +151,7 @@ class LeggedRobot(BaseTask):
         self._behaviour = None            # go1eval_host.Go1Behaviour, created by the first start_metrics(behaviour=True)
         self._trace = None                # go1eval_host.Go1Trace, created by the first start_trace()
         self._push = None                 # go1eval_host.Go1Push, created by the first push_robots()
+        self._traversal = None            # go1eval_host.Go1Terrain, created by the first start_terrain_metrics()
         if eval_cfg is not None:          # reference legged_robot.py:41-42
             self._parse_cfg(eval_cfg)
         self._parse_cfg(cfg)
@@ -447,6 +448,8 @@ class LeggedRobot(BaseTask):
                 self._behaviour.accumulate()
         if self._trace is not None and self._trace.armed:
             self._trace.record()
+        if self._traversal is not None and self._traversal.armed:
+            self._traversal.accumulate()
         if self._curriculum_sync and (self.common_step_counter + 1) % self.sim_config.curriculum_update_interval == 0:
             # ONE exchange for the last `curriculum_update_interval` steps' success counts (a slot per step), then the per-step
             # updates in order: every rank applies what a single process over the concatenated shards would
@@ -679,6 +682,64 @@ class LeggedRobot(BaseTask):
         if self._trace is None:
             raise RuntimeError("trace_recovery(): start_trace() was never called")
         return self._trace.recovery(push_row, pre, smooth, band, hold, self.dt if dt is None else dt, groups)
+
+    # ---- terrain traversal (include/go1eval.h, fifth kernel family): does a robot leave the tile it was placed on, fall or time out
+    # first, and how high are its base and feet above the ground they are over.  One more launch per step while it is armed, after the
+    # trace's; independent of start_metrics() and start_trace().
+    def place_on_terrain(self, levels, types, env_ids=None):
+        """put the training environments `env_ids` (None: all of them) on the tiles (levels[i], types[i]) of the terrain's tile grid
+        (row = level = difficulty, column = type) and reset them there: terrain_levels, terrain_types and the device env_origins
+        are set from terrain_origins[levels, types].  A scalar names one tile for all.  Raises on a configuration without a tile
+        grid (the plane), on an evaluation environment and on an index outside the grid; reads nothing from the device."""
+        ter = self.cfg.terrain
+        if ter.mesh_type not in ("heightfield", "trimesh"):
+            raise ValueError(f"place_on_terrain(): terrain.mesh_type = {ter.mesh_type!r} has no tile grid")
+        if env_ids is None:
+            ids = np.arange(self.num_train_envs, dtype=np.int64)
+        else:
+            ids = np.asarray(torch.as_tensor(env_ids).cpu(), dtype=np.int64).reshape(-1)
+        if ids.size and (ids.min() < 0 or ids.max() >= self.num_train_envs):
+            raise ValueError(f"place_on_terrain(): environment ids have to lie in [0, {self.num_train_envs}), the training environments")
+        rows, cols = (np.asarray(torch.as_tensor(v).cpu(), dtype=np.int64).reshape(-1) for v in (levels, types))
+        if rows.size not in (1, ids.size) or cols.size not in (1, ids.size):
+            raise ValueError(f"place_on_terrain(): levels and types have to name one tile, or one per environment ({ids.size})")
+        rows, cols = np.broadcast_to(rows, ids.shape), np.broadcast_to(cols, ids.shape)
+        if ids.size and (rows.min() < 0 or rows.max() >= ter.num_rows or cols.min() < 0 or cols.max() >= ter.num_cols):
+            raise ValueError(f"place_on_terrain(): a tile outside the grid of {ter.num_rows} levels x {ter.num_cols} types")
+        if ids.size == 0:
+            return
+        ids, rows, cols = (torch.from_numpy(np.array(a)).to(self.device) for a in (ids, rows, cols))
+        self.terrain_levels[ids], self.terrain_types[ids] = rows, cols
+        self.buffers.env_origins[:, ids] = ter.terrain_origins[rows, cols].t()
+        self.reset_idx(ids)
+
+    def start_terrain_metrics(self, groups, warmup_steps=0):
+        """begin a terrain measurement: `groups` = one int per environment (the row of the result table it counts towards, -1 =
+        not evaluated).  Every environment is measured from now for its first episode on its home tile (env_origins +- half a
+        tile: terrain_length x terrain_width, or env_spacing in both directions on the plane); steps with episode_length_buf <=
+        warmup_steps fold no metric"""
+        self._need_gpu_metrics("start_terrain_metrics")
+        if self._traversal is None:
+            import go1eval_host
+            ter = self.cfg.terrain
+            tile = (ter.terrain_length, ter.terrain_width) if ter.mesh_type in ("heightfield", "trimesh") else (self.cfg.env.env_spacing,) * 2
+            self._traversal = go1eval_host.Go1Terrain(self.sim_config, self.buffers, self.dt, *tile)
+        self._traversal.arm(groups, warmup_steps)
+
+    def stop_terrain_metrics(self):
+        """stop folding steps; what was measured stays readable"""
+        self._need_gpu_metrics("stop_terrain_metrics")
+        if self._traversal is not None:
+            self._traversal.disarm()
+
+    def read_terrain_metrics(self):
+        """go1eval_host.Go1Terrain.read(): {"metrics": {name: (groups, 6)}, "outcomes": {name: (groups, 6)}, "groups": (groups, 6) array
+        of envs, running, traversed, fell, timed_out, success_rate, "status", "steps", "end_step", "max_dist": per environment}: one
+        reduction launch and the device-to-host copies"""
+        self._need_gpu_metrics("read_terrain_metrics")
+        if self._traversal is None:
+            raise RuntimeError("read_terrain_metrics(): start_terrain_metrics() was never called")
+        return self._traversal.read()
 
     def render(self, mode="rgb_array"):
         """reference :1612-1620: env 0 from its recording camera, now: (240, 360, 4) uint8 RGBA"""

@@ -2,4 +2,5 @@
 (`metrics.METRICS_FNS`, `domain_randomization.DR_SETTINGS`), and `sweep.run_sweep`, which measures the ten scalar metrics on
 the device (include/go1eval.h) over a grid of commands.  `behaviour` adds the second table: gait and behaviour tracking
 (`BEHAVIOUR_FNS`, `StrideTracker`, `run_behaviour_sweep`) over a product of the other commands' values.  `response` measures the
-step response to a command switch from a trace recorded on the device, `recovery` the recovery from a push (`run_push_sweep`)."""
+step response to a command switch from a trace recorded on the device, `recovery` the recovery from a push (`run_push_sweep`), `terrain`
+which tiles of a generated terrain a policy crosses, and how (`run_terrain_sweep`)."""

@@ -39,9 +39,10 @@ def command_table(cells, num_commands, device):
     return cmd.to(device)
 
 
-def build_eval_env(preset, num_envs, seed, terrain=None):
+def build_eval_env(preset, num_envs, seed, terrain=None, configure=None):
     """(HistoryWrapper env, cfg): the training configuration with base_set() and the preset on a fresh configuration tree.
-    terrain: None keeps the training terrain; "plane" | "heightfield" | "trimesh" replaces its mesh type."""
+    terrain: None keeps the training terrain; "plane" | "heightfield" | "trimesh" replaces its mesh type.  configure(cfg), if given,
+    edits the finished configuration before the environment is built (the terrain sweep lays out its tile grid there)."""
     from go1_gym.envs.base.legged_robot_config import make_cfg
     from go1_gym.envs.go1.velocity_tracking import VelocityTrackingEasyEnv
     from go1_gym.envs.wrappers.history_wrapper import HistoryWrapper
@@ -52,6 +53,8 @@ def build_eval_env(preset, num_envs, seed, terrain=None):
     cfg.seed = seed
     if terrain is not None:
         cfg.terrain.mesh_type = terrain
+    if configure is not None:
+        configure(cfg)
     torch.manual_seed(seed)              # the terrain and the environments' first draws come from the global generators
     np.random.seed(seed)
     env = VelocityTrackingEasyEnv(sim_device=f"cuda:{torch.cuda.current_device()}", headless=True, cfg=cfg)

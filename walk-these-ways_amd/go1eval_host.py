@@ -6,7 +6,9 @@ Replaces calling the reference's go1_gym_learn/eval_metrics/metrics.py functions
 second table (gait and behaviour tracking); `Go1Trace` records a per-step time series of chosen environments on the device and
 analyses the step response to a command switch there (what the reference's scripts/play.py reads to the host step by step).
 `Go1Push` adds a chosen velocity step to the base of chosen environments with one launch, and `Go1Trace.recovery` analyses the
-trace that follows it (fall, peak velocity error, recovery time, ...).
+trace that follows it (fall, peak velocity error, recovery time, ...).  `Go1Terrain` is the fifth family: whether a robot leaves the
+terrain tile it was placed on, falls or times out first, and its height, foot clearance, stumbles and collisions above the ground
+it is over, from the simulator's own height field.
 """
 import ctypes
 import os
@@ -124,10 +126,34 @@ class Go1RecoveryBuffers(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ["trace", "values", "status", "group", "results"]]
 
 
+# ---- terrain traversal (include/go1eval.h, fifth kernel family)
+TERRAIN_NAMES = ["base_height_terrain", "feet_clearance_terrain", "swing_foot_height", "stumble", "collision"]         # enum Go1TerrainMetric
+TERRAIN_STATUS = ["running", "traversed", "fell", "timed_out"]                                                       # enum Go1TerrainStatus
+TERRAIN_OUTCOMES = ["traversed", "fell", "distance", "end_time"]                                                     # enum Go1TerrainOutcome
+TERRAIN_GROUP_FIELDS = ["envs", "running", "traversed", "fell", "timed_out", "success_rate"]                         # enum Go1TerrainGroupField
+NUM_TERRAIN, NUM_OUTCOME = 5, 4
+
+
+class Go1TerrainConfig(ctypes.Structure):
+    _fields_ = [("num_envs", ctypes.c_int32), ("warmup_steps", ctypes.c_int32), ("num_groups", ctypes.c_int32), ("hf_rows", ctypes.c_int32),
+                ("hf_cols", ctypes.c_int32), ("penalised_body_mask", ctypes.c_uint32), ("dt", ctypes.c_float), ("hf_hscale", ctypes.c_float),
+                ("hf_vscale", ctypes.c_float), ("hf_border", ctypes.c_float), ("tile_length", ctypes.c_float), ("tile_width", ctypes.c_float)]
+
+
+_TERRAIN_INPUTS = ["root_states", "commands", "contact_forces", "foot_positions", "desired_contact_states", "foot_indices", "env_origins",
+                   "height_samples", "reset_buf", "time_out_buf", "episode_length_buf"]
+_TERRAIN_STATE = ["status", "steps", "end_step", "max_dist"]
+
+
+class Go1TerrainBuffers(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in _TERRAIN_INPUTS + _ACCUMULATORS + _TERRAIN_STATE + ["group", "results"]]
+
+
 EXPORTED_SYMBOLS = ["go1eval_clear", "go1eval_accumulate", "go1eval_reduce", "go1eval_version",
                     "go1eval_behaviour_clear", "go1eval_behaviour_accumulate", "go1eval_behaviour_reduce",
                     "go1eval_trace_record", "go1eval_response", "go1eval_response_reduce",
-                    "go1eval_push", "go1eval_recovery", "go1eval_recovery_reduce"]
+                    "go1eval_push", "go1eval_recovery", "go1eval_recovery_reduce",
+                    "go1eval_terrain_clear", "go1eval_terrain_accumulate", "go1eval_terrain_reduce"]
 
 _lib = None
 
@@ -164,6 +190,9 @@ def load_library(path=None):
     lib.go1eval_push.restype = ctypes.c_int
     for fn in ("go1eval_recovery", "go1eval_recovery_reduce"):
         getattr(lib, fn).argtypes = [ctypes.POINTER(Go1RecoveryConfig), ctypes.POINTER(Go1RecoveryBuffers), ctypes.c_void_p]
+        getattr(lib, fn).restype = ctypes.c_int
+    for fn in ("go1eval_terrain_clear", "go1eval_terrain_accumulate", "go1eval_terrain_reduce"):
+        getattr(lib, fn).argtypes = [ctypes.POINTER(Go1TerrainConfig), ctypes.POINTER(Go1TerrainBuffers), ctypes.c_void_p]
         getattr(lib, fn).restype = ctypes.c_int
     lib.go1eval_version.restype = ctypes.c_char_p
     if path is None:
@@ -524,3 +553,92 @@ class Go1Push:
         """add the loaded table to the base velocities now (one launch, no sync): between two simulator steps"""
         assert self.table is not None, "load() first"
         self._check(self.lib.go1eval_push(ctypes.byref(self.cfg), ctypes.byref(self.buf), self._stream()), "go1eval_push")
+
+
+_TERRAIN_STATE_DTYPES = {"status": torch.uint8, "steps": torch.int32, "end_step": torch.int32, "max_dist": torch.float32}
+
+
+class Go1Terrain:
+    """Terrain traversal of one simulator instance, beside the tables: it owns its accumulators and the per-environment status,
+    step count and distance, and binds the simulator's height field and env_origins.  S: the simulator's Go1SimConfig, buffers:
+    its SimBuffers (device tensors), dt: the policy step in seconds, tile_length / tile_width: a tile's extent along x / y in
+    metres.  A simulator without a height field (the plane) gives height_samples = NULL: the ground is 0."""
+
+    def __init__(self, S, buffers, dt, tile_length, tile_width, lib=None):
+        self.lib = lib if lib is not None else load_library()
+        self.buffers = buffers
+        self.device = buffers.device
+        N = self.num_envs = int(S.num_envs)
+        c = self.cfg = Go1TerrainConfig()
+        c.num_envs, c.dt, c.tile_length, c.tile_width = N, float(dt), float(tile_length), float(tile_width)
+        c.penalised_body_mask = int(S.penalised_body_mask)
+        self.field = buffers.height_samples
+        if self.field is not None:
+            c.hf_rows, c.hf_cols = int(self.field.shape[0]), int(self.field.shape[1])
+            c.hf_hscale, c.hf_vscale, c.hf_border = float(S.hf_hscale), float(S.hf_vscale), float(S.hf_border)
+        else:
+            c.hf_rows, c.hf_cols, c.hf_hscale, c.hf_vscale, c.hf_border = 0, 0, 1.0, 0.0, 0.0          # not read: every sample is 0
+        self.acc = {n: torch.zeros(NUM_TERRAIN, N, dtype=dt_, device=self.device) for n, dt_ in _ACC_DTYPES.items()}
+        self.state = {n: torch.zeros(N, dtype=dt_, device=self.device) for n, dt_ in _TERRAIN_STATE_DTYPES.items()}
+        self.group = torch.full((N,), -1, dtype=torch.int32, device=self.device)
+        self.table = None
+        self.armed = False
+        self.buf = Go1TerrainBuffers()
+        self._refresh()
+
+    def _refresh(self):
+        b, B = self.buf, self.buffers
+        for n in _TERRAIN_INPUTS:
+            setattr(b, n, getattr(B, n).data_ptr() if n != "height_samples" else None)
+        if self.field is not None:
+            b.height_samples = self.field.data_ptr()
+        for n, t in list(self.acc.items()) + list(self.state.items()):
+            setattr(b, n, t.data_ptr())
+        b.group = self.group.data_ptr()
+        b.results = self.table.data_ptr() if self.table is not None else None
+
+    _stream, _check = Go1Eval._stream, Go1Eval._check
+
+    def _call(self, name):
+        self._check(getattr(self.lib, name)(ctypes.byref(self.cfg), ctypes.byref(self.buf), self._stream()), name)
+
+    def clear(self):
+        """empty accumulators, every environment RUNNING at step 0 (one launch, no sync)"""
+        self._call("go1eval_terrain_clear")
+
+    def arm(self, groups, warmup_steps=0):
+        """start a measurement (as Go1Eval.arm): sets the groups, sizes the table and clears"""
+        g = torch.as_tensor(groups).to(torch.int32).reshape(-1)
+        assert g.numel() == self.num_envs, (g.numel(), self.num_envs)
+        G = int(g.max()) + 1
+        assert G >= 1, "no environment carries a group id >= 0"
+        self.group.copy_(g)
+        self.cfg.num_groups, self.cfg.warmup_steps = G, int(warmup_steps)
+        self.table = torch.zeros(G, NUM_TERRAIN + NUM_OUTCOME + 1, NUM_FIELDS, dtype=torch.float64, device=self.device)
+        self._refresh()
+        self.clear()
+        self.armed = True
+
+    def accumulate(self):
+        """after a step: advance every RUNNING environment and fold its step (one launch, no sync)"""
+        self._call("go1eval_terrain_accumulate")
+
+    def disarm(self):
+        self.armed = False
+
+    def reduce(self):
+        """the result table [G][NUM_TERRAIN + NUM_OUTCOME + 1][NUM_FIELDS] as a device tensor (one launch, no sync)"""
+        assert self.table is not None, "arm() first"
+        self._call("go1eval_terrain_reduce")
+        return self.table
+
+    def read(self):
+        """{"metrics": {name: (G, 6) array with the columns FIELD_NAMES}, "outcomes": {name: (G, 6) array}, "groups": (G, 6) array with
+        the columns TERRAIN_GROUP_FIELDS, "status", "steps", "end_step": (N,) integer arrays, "max_dist": (N,) float32}: one launch
+        and the device-to-host copies of the table and the four state arrays"""
+        table = self.reduce().cpu().numpy()
+        out = dict(metrics={name: table[:, m, :].copy() for m, name in enumerate(TERRAIN_NAMES)},
+                   outcomes={name: table[:, NUM_TERRAIN + o, :].copy() for o, name in enumerate(TERRAIN_OUTCOMES)},
+                   groups=table[:, NUM_TERRAIN + NUM_OUTCOME, :].copy())
+        out.update({n: t.cpu().numpy() for n, t in self.state.items()})
+        return out
