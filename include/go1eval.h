@@ -639,6 +639,126 @@ int go1eval_terrain_accumulate(const Go1TerrainConfig* cfg, const Go1TerrainBuff
 /* at the end: the result table from the accumulators and the state (which it leaves as they are).  One launch.  dt <= 0: -12. */
 int go1eval_terrain_reduce(const Go1TerrainConfig* cfg, const Go1TerrainBuffers* buf, void* stream);
 
+/* ---- per-joint actuator usage (sixth kernel family; index = Go1JointMetric) ---------------------------------------------------------
+ * The five families above look at the robot as a whole; the only joint-level figure they give is max_torques, one scalar per robot.
+ * This family measures every one of the twelve joints by itself: how hard and how fast its motor is driven, how often it sits on the
+ * torque clip or on the URDF's speed limit, how much of its power is braking, how far it leans on its soft position limits, and where in
+ * the torque-speed plane it operates (a histogram).  Accumulators, folding rule and metric-row reduction are the tables'.  The
+ * reference's per-joint reward terms (_reward_torques, _reward_dof_vel, _reward_dof_acc, _reward_dof_pos_limits) are the sums over the
+ * joints of rows torque_sq, vel_sq, acc_sq and pos_limit_excess.
+ *
+ * Joint j of environment e: tau = torques[j][e], qd = dof_vel[j][e], q = dof_pos[j][e], prev = prev_dof_vel[j][e].  Ten values per joint
+ * and step, every operation an fp32 operation on fp32 values in the order written (the library is built with -ffp-contract=off: a
+ * rounding after every multiply, add and division):
+ *   torque_abs        fabsf(tau)
+ *   torque_sq         tau * tau
+ *   vel_abs           fabsf(qd)
+ *   vel_sq            qd * qd
+ *   acc_sq            d * d with d = (prev - qd) / dt  (one subtraction, one division)
+ *   power_pos         p > 0 ? p : 0 with p = tau * qd: fmaxf(p, 0) with the sign of a zero fixed (+0; fmaxf leaves it open)
+ *   power_neg         p < 0 ? -p : 0: braking, fmaxf(-p, 0) likewise.  As with fmaxf a NaN product folds 0 into both power rows (the NaN
+ *                     itself is counted in the nonfinite of torque_abs or vel_abs); an infinite product is counted in nonfinite here.
+ *   pos_limit_excess  (lo < 0 ? -lo : 0) + (hi > 0 ? hi : 0) with lo = q - pos_lower[j], hi = q - pos_upper[j]: the reference's
+ *                     -min(lo, 0) + max(hi, 0), one add.  A NaN q gives NaN, as the reference's clip hands it on.
+ *   torque_saturated  1 if fabsf(tau) >= soft_torque_limit * torque_limit[j] (one multiply), else 0: the limit the SIMULATOR clips at, not
+ *                     a motor model.  A NaN compares false: 0.
+ *   vel_saturated     1 if fabsf(qd) >= soft_vel_limit * vel_limit[j], else 0
+ *
+ * The torque-speed histogram of a joint has GO1JOINT_TAU_BINS x GO1JOINT_VEL_BINS cells.  For x with limit L (tau with torque_limit[j],
+ * qd with vel_limit[j]; the soft factors play no part) the bin is b = floorf((x / L + 1.0f) * 4.0f), clamped to [0, 7] AS A FLOAT and
+ * only then converted to an integer (the terrain family's rule: no value outside an int's range is ever converted).  So x = -L lands
+ * in bin 0, x = 0 (of either sign) in bin 4, x >= L in bin 7 and x < -L in bin 0; bin k covers [L (k / 4 - 1), L ((k + 1) / 4 - 1)).
+ * (The edges are those of the fp32 expression: x / L + 1 is rounded, so a value within an ulp of 1 of an edge may count in the bin beside it.)
+ * The cell is tau_bin * GO1JOINT_VEL_BINS + vel_bin.  A sample enters the histogram on the steps that fold metrics, and only when
+ * both tau and qd are finite.
+ *
+ * go1eval_joint_accumulate: one thread per (joint, environment), no atomics, no LDS; every word has one writer.  The launch is
+ * one-dimensional: 12 * ceil(N / 256) blocks of 256 threads, block k works on joint k / ceil(N / 256) and its lanes on consecutive
+ * environments, so a joint's limits are uniform per block and every load and store of a row is one contiguous run over a wavefront (the
+ * one exception: the histogram word, whose cell differs from lane to lane).  Per (j, e), in this order:
+ *   1. the thread of joint 0: steps[e] += 1, and resets[e] += 1 if reset_buf[e] != 0.
+ *   2. reset_buf[e] != 0: the step reset the environment; no metric and no histogram sample is folded.
+ *   3. otherwise, episode_length_buf[e] <= warmup_steps: nothing is folded (the step counted in steps only).
+ *   4. otherwise the ten values are folded in the order of Go1JointMetric into row j * GO1EVAL_NUM_JOINT + metric by the folding rule of
+ *      go1eval_accumulate (a non-finite value counts in nonfinite and enters nothing else), then the histogram sample.
+ *   5. on EVERY step, folded or not: prev_dof_vel[j][e] = qd.
+ *   The previous velocity is the family's own copy: go1eval_joint_clear takes it from dof_vel, and every accumulate leaves the current
+ *   dof_vel there.  After a reset step that is the post-reset velocity, which the simulator sets to 0: what the reference's
+ *   last_dof_vel[env_ids] = 0 gives.  (The simulator's own last_dof_vel is no use: after a step it already equals dof_vel.)
+ * go1eval_joint_clear: one launch of the same shape: accumulators as go1eval_clear, the histogram 0, steps = resets = 0,
+ *   prev_dof_vel = dof_vel.
+ * go1eval_joint_reduce: ONE launch of GO1EVAL_REDUCE_THREADS-thread workgroups: num_groups * (12 * GO1EVAL_NUM_JOINT + 1) of them
+ *   write results[num_groups][12 * GO1EVAL_NUM_JOINT + 1][GO1EVAL_NUM_FIELDS], then num_groups * 12 write
+ *   hist_results[num_groups][12][GO1JOINT_TAU_BINS][GO1JOINT_VEL_BINS].
+ *   Rows j * GO1EVAL_NUM_JOINT + metric: the metric rows of go1eval_reduce (the same device function, the same fixed combination order).
+ *   The last row of a group (index = Go1JointGroupField): environments, steps (sum of steps[e]), resets, then 0, 0, 0 (sums in the same
+ *   fixed order).
+ *   Histogram, one workgroup per (group, joint): thread t owns cell t % 64 and adds hist[j][t % 64][e] of the group's environments
+ *   e = t / 64, t / 64 + 4, t / 64 + 8, ... in ascending order as uint64; then a fixed tree over the four slices (thread t takes
+ *   thread t + 128, then thread t + 64) and threads 0 .. 63 write their cell.
+ * Refused before any launch: -1 no config, no buffers or num_envs <= 0;  -2 an accumulator, the histogram or a state array is missing;
+ *   -3 an input is missing (go1eval_joint_clear reads dof_vel only, go1eval_joint_reduce none);  -5 no group, no table, no histogram
+ *   table or num_groups <= 0 (go1eval_joint_reduce);  -12 (go1eval_joint_accumulate) dt, soft_torque_limit, soft_vel_limit, a
+ *   torque_limit[j] or a vel_limit[j] that is not finite and positive, or a joint without pos_lower[j] <= pos_upper[j] (a NaN is refused).
+ */
+#define GO1EVAL_NUM_JOINT 10
+#define GO1JOINT_TAU_BINS 8
+#define GO1JOINT_VEL_BINS 8
+
+enum Go1JointMetric {
+  GO1JOINT_TORQUE_ABS = 0, GO1JOINT_TORQUE_SQ = 1, GO1JOINT_VEL_ABS = 2, GO1JOINT_VEL_SQ = 3, GO1JOINT_ACC_SQ = 4, GO1JOINT_POWER_POS = 5,
+  GO1JOINT_POWER_NEG = 6, GO1JOINT_POS_LIMIT_EXCESS = 7, GO1JOINT_TORQUE_SATURATED = 8, GO1JOINT_VEL_SATURATED = 9
+};
+/* columns of a group's own row (row 12 * GO1EVAL_NUM_JOINT) of the joint table */
+enum Go1JointGroupField { GO1JOINT_G_ENVS = 0, GO1JOINT_G_STEPS = 1, GO1JOINT_G_RESETS = 2 };
+
+typedef struct Go1JointConfig {
+  int32_t num_envs;            /* N of the simulator's SoA buffers */
+  int32_t warmup_steps;        /* steps with episode_length_buf <= warmup_steps fold nothing */
+  int32_t num_groups;          /* G of the result tables */
+  float dt;                    /* s, the policy step: acc_sq divides by it */
+  float soft_torque_limit;     /* torque_saturated compares with soft_torque_limit * torque_limit[j] */
+  float soft_vel_limit;        /* vel_saturated compares with soft_vel_limit * vel_limit[j] */
+  float torque_limit[12];      /* N m: the limit the simulator clips the torque at; the histogram's torque scale */
+  float vel_limit[12];         /* rad/s: the URDF's speed limit; the histogram's speed scale */
+  float pos_lower[12];         /* rad: the simulator's dof_pos_soft_lower */
+  float pos_upper[12];         /* rad: the simulator's dof_pos_soft_upper */
+} Go1JointConfig;
+
+typedef struct Go1JointBuffers {
+  /* read by go1eval_joint_accumulate (go1eval_joint_clear reads dof_vel) */
+  const float* torques;               /* [12][N] */
+  const float* dof_vel;               /* [12][N] */
+  const float* dof_pos;               /* [12][N] */
+  const uint8_t* reset_buf;           /* [N] */
+  const int32_t* episode_length_buf;  /* [N] */
+  /* accumulators, [12 * GO1EVAL_NUM_JOINT][N]: row j * GO1EVAL_NUM_JOINT + metric */
+  uint32_t* count;
+  double* sum;
+  double* sumsq;
+  float* min;
+  float* max;
+  uint32_t* nonfinite;
+  /* state */
+  float* prev_dof_vel;                /* [12][N] */
+  uint32_t* steps;                    /* [N]: accumulate launches since the clear */
+  uint32_t* resets;                   /* [N]: of those, the steps that reset the environment */
+  uint32_t* hist;                     /* [12][GO1JOINT_TAU_BINS * GO1JOINT_VEL_BINS][N] */
+  /* go1eval_joint_reduce */
+  const int32_t* group;               /* [N] */
+  double* results;                    /* [num_groups][12 * GO1EVAL_NUM_JOINT + 1][GO1EVAL_NUM_FIELDS] */
+  uint64_t* hist_results;             /* [num_groups][12][GO1JOINT_TAU_BINS][GO1JOINT_VEL_BINS] */
+} Go1JointBuffers;
+
+/* empty accumulators and histogram, prev_dof_vel = dof_vel.  One launch, one thread per (joint, environment). */
+int go1eval_joint_clear(const Go1JointConfig* cfg, const Go1JointBuffers* buf, void* stream);
+
+/* after a simulator step: fold the step of every joint.  One launch, one thread per (joint, environment).  Limits refused: -12. */
+int go1eval_joint_accumulate(const Go1JointConfig* cfg, const Go1JointBuffers* buf, void* stream);
+
+/* at the end: both result tables from the accumulators and the histogram (which it leaves as they are).  One launch. */
+int go1eval_joint_reduce(const Go1JointConfig* cfg, const Go1JointBuffers* buf, void* stream);
+
 /* "go1eval <version> (gfx950) go1-src:<16 hex digits of the source hash>" */
 const char* go1eval_version(void);
 

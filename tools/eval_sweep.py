@@ -37,6 +37,13 @@ types (`--mesh trimesh | heightfield`, `--proportions P ...` for the mix of type
 swing above the ground.  `<out>/eval/<preset>_terrain.json` is written and the grid (rows = difficulty, columns = terrain type) is
 printed and appended to `<out>/eval/<preset>_terrain.md`.  (`--terrain MESH` with a value keeps its meaning for the other sweeps:
 the mesh type of their terrain.)
+
+    python tools/eval_sweep.py --checkpoint RUN_DIR/checkpoints --out RUN_DIR --joints --vx 0.5 1.0 1.5
+
+With `--joints` the velocity grid is swept with the per-joint table armed beside the scalar one (go1_gym_learn.eval_metrics.joints):
+torque, speed, acceleration, driving and braking power, soft-limit excess and the shares of steps at the torque clip and at the
+URDF's speed limit for each of the twelve joints, and a torque-speed histogram per joint.  `<out>/eval/<preset>_joints.json` and the
+torque-speed envelope `<preset>_envelope.png` are written and the per-joint table is printed and appended to `<preset>_joints.md`.
 Run on the GPU box."""
 import argparse
 import json
@@ -123,6 +130,7 @@ def parse_args(argv=None):
     ap.add_argument("--magnitude", nargs="+", type=float, default=None, help="with --push: velocity steps in m/s; 0 is the control cell")
     ap.add_argument("--direction", nargs="+", type=float, default=None,
                     help="with --push: directions in degrees in the robot's heading frame (0 a shove from behind, 90 a push to the left)")
+    ap.add_argument("--joints", action="store_true", help="measure per-joint actuator usage over the velocity grid, beside the scalar table")
     ap.add_argument("--out", required=True)
     a = ap.parse_args(argv)
     a.tiles = a.terrain == "tiles"
@@ -140,6 +148,8 @@ def parse_args(argv=None):
         if a.rows < 1 or a.cols < 1 or a.window < 1:
             ap.error("--rows, --cols and --window have to be at least 1")
     a.vx = a.vx or [0.5, 1.0, 1.5]
+    if a.joints and (a.tiles or a.response or a.behaviour or a.push):
+        ap.error("--joints excludes --terrain (bare), --response, --behaviour and --push")
     if a.switch and not a.response:
         ap.error("--switch needs --response")
     if a.trace_envs and not (a.response or a.push):
@@ -221,6 +231,21 @@ def run_terrain(a, policy):
             f.write(text + "\n")
 
 
+def run_joints(a, policy, grid):
+    from go1_gym_learn.eval_metrics import joints
+    for preset in a.presets:
+        res = joints.run_joint_sweep(policy, preset, grid, num_envs=a.envs, steps=a.steps, warmup_steps=a.warmup_steps, seed=a.seed, terrain=a.terrain)
+        stem = os.path.join(a.out, "eval", preset)
+        with open(stem + "_joints.json", "w") as f:
+            json.dump(joints.joint_to_json(res), f, indent=1)
+        text = f"### {preset}: {a.envs} environments, {a.steps} steps, vx {a.vx}, per-joint actuator usage\n\n" + joints.joint_markdown_table(res) + "\n"
+        print(text)
+        with open(stem + "_joints.md", "a") as f:
+            f.write(text + "\n")
+        joints.plot_envelope(res["hist"], stem + "_envelope.png", torque_limit=res["torque_limit"][0], vel_limit=res["vel_limit"][:3],
+                             soft_torque_limit=res["soft_torque_limit"], soft_vel_limit=res["soft_vel_limit"])
+
+
 def behaviour_axes(a):
     """{command name: [values]} of the --axis options, in the order given"""
     from go1_gym_learn.eval_metrics.behaviour import COMMAND_INDEX
@@ -247,6 +272,8 @@ def main(argv=None):
         return run_push(a, policy)
     if a.tiles:
         return run_terrain(a, policy)
+    if a.joints:
+        return run_joints(a, policy, grid)
     if a.behaviour:
         from go1_gym_learn.eval_metrics import behaviour
         axes = behaviour_axes(a)

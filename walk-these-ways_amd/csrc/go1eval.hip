@@ -19,6 +19,9 @@
 // that carries its status, step count and distance ([N], one writer per word) and reads fifteen int16 samples of the height field
 // under its base and feet, the family's only scattered loads, issued as one batch; the reduction goes through reduce_metric_row
 // (metric rows, and outcome rows over one computed value per environment) and status_row.  tests/terrain_ref.py is the model.
+// joint_accumulate_kernel / joint_reduce_kernel: per-joint actuator usage: one thread per (joint, environment) in a one-dimensional
+// launch whose blocks each belong to one joint, so the joint's limits are uniform per block and every row access is a contiguous run
+// (the histogram word alone is scattered); metric rows through reduce_metric_row, the histogram by its own uint64 sums.  tests/joint_ref.py.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -731,6 +734,128 @@ extern "C" __global__ void __launch_bounds__(RT) terrain_reduce_kernel(const Ter
   out[GO1TERRAIN_G_SUCCESS_RATE] = ended > 0.0 ? out[GO1TERRAIN_G_TRAVERSED] / ended : (double)NAN;
 }
 
+// ---- per-joint actuator usage ---------------------------------------------------------------------------------------------------
+constexpr int NJ = GO1EVAL_NUM_JOINT, DOF = 12, TB = GO1JOINT_TAU_BINS, VB = GO1JOINT_VEL_BINS, CELLS = TB * VB;
+static_assert(RT == 4 * CELLS, "joint_reduce_kernel: four slices of environments per histogram cell");
+
+struct JointArgs {
+  Go1JointConfig c;
+  Go1JointBuffers b;
+};
+
+namespace {
+// the histogram bin of x on the scale L: clamped as a float, then converted (see the header)
+__device__ __forceinline__ int joint_bin(float x, float L, int bins) {
+  const float b = floorf((x / L + 1.0f) * 4.0f), last = (float)(bins - 1);
+  return (int)(b > last ? last : (b > 0.0f ? b : 0.0f));
+}
+// the launch of one thread per (joint, environment): block k is joint k / blocks_per_joint, its lanes consecutive environments
+__device__ __forceinline__ bool joint_thread(int N, int* j, int* e) {
+  const int per_joint = (N + ACC_THREADS - 1) / ACC_THREADS;
+  *j = (int)blockIdx.x / per_joint;
+  *e = ((int)blockIdx.x % per_joint) * ACC_THREADS + (int)threadIdx.x;
+  return *j < DOF && *e < N;
+}
+}  // namespace
+
+extern "C" __global__ void __launch_bounds__(ACC_THREADS) joint_clear_kernel(const JointArgs A) {
+  const int N = A.c.num_envs;
+  int j, e;
+  if (!joint_thread(N, &j, &e)) return;
+  const Go1JointBuffers& b = A.b;
+  for (int m = 0; m < NJ; m++) {
+    const size_t i = (size_t)(j * NJ + m) * N + e;
+    b.count[i] = 0u; b.nonfinite[i] = 0u; b.sum[i] = 0.0; b.sumsq[i] = 0.0; b.min[i] = INFINITY; b.max[i] = -INFINITY;
+  }
+  for (int cell = 0; cell < CELLS; cell++) b.hist[(size_t)(j * CELLS + cell) * N + e] = 0u;
+  b.prev_dof_vel[(size_t)j * N + e] = b.dof_vel[(size_t)j * N + e];
+  if (j == 0) { b.steps[e] = 0u; b.resets[e] = 0u; }
+}
+
+extern "C" __global__ void __launch_bounds__(ACC_THREADS) joint_accumulate_kernel(const JointArgs A) {
+  const Go1JointConfig& c = A.c;
+  const int N = c.num_envs;
+  int j, e;
+  if (!joint_thread(N, &j, &e)) return;
+  const Go1JointBuffers& b = A.b;
+  const size_t i = (size_t)j * N + e;
+  const bool reset = b.reset_buf[e] != 0;
+  if (j == 0) {
+    b.steps[e] += 1u;
+    if (reset) b.resets[e] += 1u;
+  }
+  const float qd = b.dof_vel[i];
+  if (!reset && b.episode_length_buf[e] > c.warmup_steps) {
+    const float tau = b.torques[i], q = b.dof_pos[i], prev = b.prev_dof_vel[i];
+    const float tau_limit = c.torque_limit[j], vel_limit = c.vel_limit[j];            // (uniform per block)
+    const float d = (prev - qd) / c.dt, p = tau * qd;
+    const float below = q - c.pos_lower[j], above = q - c.pos_upper[j];
+    float excess = (below < 0.0f ? -below : 0.0f) + (above > 0.0f ? above : 0.0f);
+    if (q != q) excess = q;                                                            // (the selects would drop the NaN)
+    const int row = j * NJ;
+    fold(b, row + GO1JOINT_TORQUE_ABS, N, e, fabsf(tau));
+    fold(b, row + GO1JOINT_TORQUE_SQ, N, e, tau * tau);
+    fold(b, row + GO1JOINT_VEL_ABS, N, e, fabsf(qd));
+    fold(b, row + GO1JOINT_VEL_SQ, N, e, qd * qd);
+    fold(b, row + GO1JOINT_ACC_SQ, N, e, d * d);
+    fold(b, row + GO1JOINT_POWER_POS, N, e, p > 0.0f ? p : 0.0f);
+    fold(b, row + GO1JOINT_POWER_NEG, N, e, p < 0.0f ? -p : 0.0f);
+    fold(b, row + GO1JOINT_POS_LIMIT_EXCESS, N, e, excess);
+    fold(b, row + GO1JOINT_TORQUE_SATURATED, N, e, fabsf(tau) >= c.soft_torque_limit * tau_limit ? 1.0f : 0.0f);
+    fold(b, row + GO1JOINT_VEL_SATURATED, N, e, fabsf(qd) >= c.soft_vel_limit * vel_limit ? 1.0f : 0.0f);
+    if (isfinite(tau) && isfinite(qd)) {
+      const int cell = joint_bin(tau, tau_limit, TB) * VB + joint_bin(qd, vel_limit, VB);   // in [0, CELLS): both bins are clamped
+      b.hist[(size_t)(j * CELLS + cell) * N + e] += 1u;
+    }
+  }
+  b.prev_dof_vel[i] = qd;
+}
+
+extern "C" __global__ void __launch_bounds__(RT) joint_reduce_kernel(const JointArgs A) {
+  __shared__ double lds[NF][RT];
+  __shared__ unsigned long long cells[RT];
+  constexpr int rows = DOF * NJ + 1;
+  const int N = A.c.num_envs, G = A.c.num_groups;
+  const int t = (int)threadIdx.x;
+  const Go1JointBuffers& b = A.b;
+  if ((int)blockIdx.x < G * rows) {
+    const int g = (int)blockIdx.x / rows, m = (int)blockIdx.x % rows;
+    double* out = b.results + ((size_t)g * rows + m) * NF;
+    if (m != rows - 1) { reduce_metric_row(b, g, m, N, lds, out); return; }
+    // the group's own row: a0 envs, a1 steps, a2 resets
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+    for (int e = t; e < N; e += RT) {
+      if (b.group[e] != g) continue;
+      a0 += 1.0; a1 += (double)b.steps[e]; a2 += (double)b.resets[e];
+    }
+    lds[0][t] = a0; lds[1][t] = a1; lds[2][t] = a2;
+    __syncthreads();
+    for (int s = RT / 2; s > 0; s >>= 1) {
+      if (t < s) {
+        for (int f = 0; f < 3; f++) lds[f][t] += lds[f][t + s];
+      }
+      __syncthreads();
+    }
+    if (t != 0) return;
+    out[GO1JOINT_G_ENVS] = lds[0][0]; out[GO1JOINT_G_STEPS] = lds[1][0]; out[GO1JOINT_G_RESETS] = lds[2][0];
+    out[3] = 0.0; out[4] = 0.0; out[5] = 0.0;
+    return;
+  }
+  // the histogram of (group, joint): thread t owns cell t % 64 and the environments t / 64, t / 64 + 4, ...
+  const int k = (int)blockIdx.x - G * rows;
+  const int g = k / DOF, j = k % DOF, cell = t % CELLS;
+  const uint32_t* h = b.hist + (size_t)(j * CELLS + cell) * N;
+  unsigned long long sum = 0ull;
+  for (int e = t / CELLS; e < N; e += RT / CELLS) {
+    if (b.group[e] == g) sum += (unsigned long long)h[e];
+  }
+  cells[t] = sum;
+  __syncthreads();
+  if (t < 2 * CELLS) cells[t] += cells[t + 2 * CELLS];
+  __syncthreads();
+  if (t < CELLS) b.hist_results[((size_t)g * DOF + j) * CELLS + t] = cells[t] + cells[t + CELLS];
+}
+
 namespace {
 int check(const Go1EvalConfig* cfg, const Go1EvalBuffers* buf) {
   if (!cfg || !buf || cfg->num_envs <= 0) return -1;
@@ -921,6 +1046,46 @@ extern "C" int go1eval_terrain_reduce(const Go1TerrainConfig* cfg, const Go1Terr
   if (!(cfg->dt > 0.0f)) return -12;
   const TerrainArgs A = args_of(cfg, buf);
   hipLaunchKernelGGL(terrain_reduce_kernel, dim3((unsigned)(cfg->num_groups * (NTM + NTO + 1))), dim3(RT), 0, (hipStream_t)stream, A);
+  return hipGetLastError() == hipSuccess ? 0 : -20;
+}
+
+namespace {
+int check(const Go1JointConfig* cfg, const Go1JointBuffers* buf) {
+  if (!cfg || !buf || cfg->num_envs <= 0) return -1;
+  if (!buf->count || !buf->sum || !buf->sumsq || !buf->min || !buf->max || !buf->nonfinite || !buf->prev_dof_vel || !buf->steps ||
+      !buf->resets || !buf->hist) return -2;
+  return 0;
+}
+JointArgs args_of(const Go1JointConfig* cfg, const Go1JointBuffers* buf) { JointArgs A; A.c = *cfg; A.b = *buf; return A; }
+dim3 joint_grid(int n) { return dim3((unsigned)(DOF * ((n + ACC_THREADS - 1) / ACC_THREADS))); }
+bool positive(float x) { return x > 0.0f && x <= 3.402823466e38f; }            // finite and positive (a NaN fails both)
+}  // namespace
+
+extern "C" int go1eval_joint_clear(const Go1JointConfig* cfg, const Go1JointBuffers* buf, void* stream) {
+  if (int rc = check(cfg, buf)) return rc;
+  if (!buf->dof_vel) return -3;
+  const JointArgs A = args_of(cfg, buf);
+  hipLaunchKernelGGL(joint_clear_kernel, joint_grid(cfg->num_envs), dim3(ACC_THREADS), 0, (hipStream_t)stream, A);
+  return hipGetLastError() == hipSuccess ? 0 : -20;
+}
+
+extern "C" int go1eval_joint_accumulate(const Go1JointConfig* cfg, const Go1JointBuffers* buf, void* stream) {
+  if (int rc = check(cfg, buf)) return rc;
+  if (!buf->torques || !buf->dof_vel || !buf->dof_pos || !buf->reset_buf || !buf->episode_length_buf) return -3;
+  if (!(positive(cfg->dt) && positive(cfg->soft_torque_limit) && positive(cfg->soft_vel_limit))) return -12;
+  for (int j = 0; j < DOF; j++) {
+    if (!(positive(cfg->torque_limit[j]) && positive(cfg->vel_limit[j]) && cfg->pos_lower[j] <= cfg->pos_upper[j])) return -12;
+  }
+  const JointArgs A = args_of(cfg, buf);
+  hipLaunchKernelGGL(joint_accumulate_kernel, joint_grid(cfg->num_envs), dim3(ACC_THREADS), 0, (hipStream_t)stream, A);
+  return hipGetLastError() == hipSuccess ? 0 : -20;
+}
+
+extern "C" int go1eval_joint_reduce(const Go1JointConfig* cfg, const Go1JointBuffers* buf, void* stream) {
+  if (int rc = check(cfg, buf)) return rc;
+  if (cfg->num_groups <= 0 || !buf->group || !buf->results || !buf->hist_results) return -5;
+  const JointArgs A = args_of(cfg, buf);
+  hipLaunchKernelGGL(joint_reduce_kernel, dim3((unsigned)(cfg->num_groups * (DOF * NJ + 1 + DOF))), dim3(RT), 0, (hipStream_t)stream, A);
   return hipGetLastError() == hipSuccess ? 0 : -20;
 }
 

@@ -152,6 +152,7 @@ class LeggedRobot(BaseTask):
         self._trace = None                # go1eval_host.Go1Trace, created by the first start_trace()
         self._push = None                 # go1eval_host.Go1Push, created by the first push_robots()
         self._traversal = None            # go1eval_host.Go1Terrain, created by the first start_terrain_metrics()
+        self._joints = None               # go1eval_host.Go1Joints, created by the first start_joint_metrics()
         if eval_cfg is not None:          # reference legged_robot.py:41-42
             self._parse_cfg(eval_cfg)
         self._parse_cfg(cfg)
@@ -450,6 +451,8 @@ class LeggedRobot(BaseTask):
             self._trace.record()
         if self._traversal is not None and self._traversal.armed:
             self._traversal.accumulate()
+        if self._joints is not None and self._joints.armed:
+            self._joints.accumulate()
         if self._curriculum_sync and (self.common_step_counter + 1) % self.sim_config.curriculum_update_interval == 0:
             # ONE exchange for the last `curriculum_update_interval` steps' success counts (a slot per step), then the per-step
             # updates in order: every rank applies what a single process over the concatenated shards would
@@ -740,6 +743,37 @@ class LeggedRobot(BaseTask):
         if self._traversal is None:
             raise RuntimeError("read_terrain_metrics(): start_terrain_metrics() was never called")
         return self._traversal.read()
+
+    # ---- per-joint actuator usage (include/go1eval.h, sixth kernel family): ten values per joint and step and a torque-speed histogram
+    # per joint.  One more launch per step while it is armed, after the terrain family's; independent of the other measurements.
+    def start_joint_metrics(self, groups, warmup_steps=0):
+        """begin a joint measurement: `groups` = one int per environment (the row of the result tables it counts towards, -1 = not
+        evaluated); steps with episode_length_buf <= warmup_steps fold nothing.  Saturation is tested against
+        rewards.soft_torque_limit x the simulator's torque limit and rewards.soft_dof_vel_limit x the URDF's speed limit (a factor
+        the configuration does not carry is 1)"""
+        self._need_gpu_metrics("start_joint_metrics")
+        if self._joints is None:
+            import go1eval_host
+            rewards = self.cfg.rewards
+            self._joints = go1eval_host.Go1Joints(self.sim_config, self.buffers, self.dt, H._DOF_VELOCITY,
+                                                  soft_torque_limit=float(getattr(rewards, "soft_torque_limit", 1.0)),
+                                                  soft_vel_limit=float(getattr(rewards, "soft_dof_vel_limit", 1.0)))
+        self._joints.arm(groups, warmup_steps)
+
+    def stop_joint_metrics(self):
+        """stop folding steps; what was measured stays readable"""
+        self._need_gpu_metrics("stop_joint_metrics")
+        if self._joints is not None:
+            self._joints.disarm()
+
+    def read_joint_metrics(self):
+        """go1eval_host.Go1Joints.read(): {"metrics": {name: (groups, 12, 6)}, "groups": (groups, 3) array of envs, steps, resets, "hist":
+        (groups, 12, 8, 8) torque-bin x speed-bin counts, "tau_edges", "vel_edges": (12, 9), and the per-environment "steps", "resets",
+        "prev_dof_vel", "env_hist"}: one reduction launch and the device-to-host copies"""
+        self._need_gpu_metrics("read_joint_metrics")
+        if self._joints is None:
+            raise RuntimeError("read_joint_metrics(): start_joint_metrics() was never called")
+        return self._joints.read()
 
     def render(self, mode="rgb_array"):
         """reference :1612-1620: env 0 from its recording camera, now: (240, 360, 4) uint8 RGBA"""

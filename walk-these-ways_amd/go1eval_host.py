@@ -8,7 +8,9 @@ analyses the step response to a command switch there (what the reference's scrip
 `Go1Push` adds a chosen velocity step to the base of chosen environments with one launch, and `Go1Trace.recovery` analyses the
 trace that follows it (fall, peak velocity error, recovery time, ...).  `Go1Terrain` is the fifth family: whether a robot leaves the
 terrain tile it was placed on, falls or times out first, and its height, foot clearance, stumbles and collisions above the ground
-it is over, from the simulator's own height field.
+it is over, from the simulator's own height field.  `Go1Joints` is the sixth: ten values per joint and step (torque, speed,
+acceleration, driving and braking power, soft-limit excess, saturation at the torque clip and at the URDF's speed limit) and a
+torque-speed histogram per joint.
 """
 import ctypes
 import os
@@ -149,11 +151,34 @@ class Go1TerrainBuffers(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in _TERRAIN_INPUTS + _ACCUMULATORS + _TERRAIN_STATE + ["group", "results"]]
 
 
+# ---- per-joint actuator usage (include/go1eval.h, sixth kernel family)
+JOINT_NAMES = ["torque_abs", "torque_sq", "vel_abs", "vel_sq", "acc_sq", "power_pos", "power_neg", "pos_limit_excess", "torque_saturated",
+               "vel_saturated"]                                                                                      # enum Go1JointMetric
+JOINT_GROUP_FIELDS = ["envs", "steps", "resets"]                                                                     # enum Go1JointGroupField
+DOF_NAMES = [f"{leg}_{part}_joint" for leg in ("FL", "FR", "RL", "RR") for part in ("hip", "thigh", "calf")]         # the simulator's joint order
+NUM_DOF, NUM_JOINT, JOINT_TAU_BINS, JOINT_VEL_BINS = 12, 10, 8, 8
+
+
+class Go1JointConfig(ctypes.Structure):
+    _fields_ = [("num_envs", ctypes.c_int32), ("warmup_steps", ctypes.c_int32), ("num_groups", ctypes.c_int32), ("dt", ctypes.c_float),
+                ("soft_torque_limit", ctypes.c_float), ("soft_vel_limit", ctypes.c_float), ("torque_limit", ctypes.c_float * 12),
+                ("vel_limit", ctypes.c_float * 12), ("pos_lower", ctypes.c_float * 12), ("pos_upper", ctypes.c_float * 12)]
+
+
+_JOINT_INPUTS = ["torques", "dof_vel", "dof_pos", "reset_buf", "episode_length_buf"]
+_JOINT_STATE = ["prev_dof_vel", "steps", "resets", "hist"]
+
+
+class Go1JointBuffers(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in _JOINT_INPUTS + _ACCUMULATORS + _JOINT_STATE + ["group", "results", "hist_results"]]
+
+
 EXPORTED_SYMBOLS = ["go1eval_clear", "go1eval_accumulate", "go1eval_reduce", "go1eval_version",
                     "go1eval_behaviour_clear", "go1eval_behaviour_accumulate", "go1eval_behaviour_reduce",
                     "go1eval_trace_record", "go1eval_response", "go1eval_response_reduce",
                     "go1eval_push", "go1eval_recovery", "go1eval_recovery_reduce",
-                    "go1eval_terrain_clear", "go1eval_terrain_accumulate", "go1eval_terrain_reduce"]
+                    "go1eval_terrain_clear", "go1eval_terrain_accumulate", "go1eval_terrain_reduce",
+                    "go1eval_joint_clear", "go1eval_joint_accumulate", "go1eval_joint_reduce"]
 
 _lib = None
 
@@ -193,6 +218,9 @@ def load_library(path=None):
         getattr(lib, fn).restype = ctypes.c_int
     for fn in ("go1eval_terrain_clear", "go1eval_terrain_accumulate", "go1eval_terrain_reduce"):
         getattr(lib, fn).argtypes = [ctypes.POINTER(Go1TerrainConfig), ctypes.POINTER(Go1TerrainBuffers), ctypes.c_void_p]
+        getattr(lib, fn).restype = ctypes.c_int
+    for fn in ("go1eval_joint_clear", "go1eval_joint_accumulate", "go1eval_joint_reduce"):
+        getattr(lib, fn).argtypes = [ctypes.POINTER(Go1JointConfig), ctypes.POINTER(Go1JointBuffers), ctypes.c_void_p]
         getattr(lib, fn).restype = ctypes.c_int
     lib.go1eval_version.restype = ctypes.c_char_p
     if path is None:
@@ -641,4 +669,99 @@ class Go1Terrain:
                    outcomes={name: table[:, NUM_TERRAIN + o, :].copy() for o, name in enumerate(TERRAIN_OUTCOMES)},
                    groups=table[:, NUM_TERRAIN + NUM_OUTCOME, :].copy())
         out.update({n: t.cpu().numpy() for n, t in self.state.items()})
+        return out
+
+
+def joint_edges(limit):
+    """the nine edges of the eight histogram bins on the scale `limit`: bin k covers [edges[k], edges[k + 1]); values beyond the two
+    ends are counted in the first and the last bin"""
+    return float(limit) * (np.arange(JOINT_TAU_BINS + 1) / 4.0 - 1.0)
+
+
+class Go1Joints:
+    """Per-joint actuator usage of one simulator instance, beside the tables: it owns its accumulators ([12 * 10][N]), its copy of the
+    previous joint velocities and the per-environment torque-speed histogram ([12][64][N]).  S: the simulator's Go1SimConfig,
+    buffers: its SimBuffers (device tensors), dt: the policy step in seconds, vel_limit: the twelve URDF speed limits in rad/s,
+    soft_torque_limit / soft_vel_limit: the factors of the two saturation tests.  The torque limits and the soft position limits are
+    the simulator's own (S.torque_limits, S.dof_pos_soft_lower / upper)."""
+
+    def __init__(self, S, buffers, dt, vel_limit, soft_torque_limit=1.0, soft_vel_limit=1.0, lib=None):
+        self.lib = lib if lib is not None else load_library()
+        self.buffers = buffers
+        self.device = buffers.device
+        N = self.num_envs = int(S.num_envs)
+        c = self.cfg = Go1JointConfig()
+        c.num_envs, c.dt, c.soft_torque_limit, c.soft_vel_limit = N, float(dt), float(soft_torque_limit), float(soft_vel_limit)
+        for j in range(NUM_DOF):
+            c.torque_limit[j], c.vel_limit[j] = float(S.torque_limits[j]), float(vel_limit[j])
+            c.pos_lower[j], c.pos_upper[j] = float(S.dof_pos_soft_lower[j]), float(S.dof_pos_soft_upper[j])
+        self.acc = {n: torch.zeros(NUM_DOF * NUM_JOINT, N, dtype=dt_, device=self.device) for n, dt_ in _ACC_DTYPES.items()}
+        self.state = dict(prev_dof_vel=torch.zeros(NUM_DOF, N, dtype=torch.float32, device=self.device),
+                          steps=torch.zeros(N, dtype=torch.int32, device=self.device), resets=torch.zeros(N, dtype=torch.int32, device=self.device),
+                          hist=torch.zeros(NUM_DOF, JOINT_TAU_BINS * JOINT_VEL_BINS, N, dtype=torch.int32, device=self.device))
+        self.group = torch.full((N,), -1, dtype=torch.int32, device=self.device)
+        self.table = self.hist_table = None
+        self.armed = False
+        self.buf = Go1JointBuffers()
+        self._refresh()
+
+    def _refresh(self):
+        b, B = self.buf, self.buffers
+        for n in _JOINT_INPUTS:
+            setattr(b, n, getattr(B, n).data_ptr())
+        for n, t in list(self.acc.items()) + list(self.state.items()):
+            setattr(b, n, t.data_ptr())
+        b.group = self.group.data_ptr()
+        b.results = self.table.data_ptr() if self.table is not None else None
+        b.hist_results = self.hist_table.data_ptr() if self.hist_table is not None else None
+
+    _stream, _check = Go1Eval._stream, Go1Eval._check
+
+    def _call(self, name):
+        self._check(getattr(self.lib, name)(ctypes.byref(self.cfg), ctypes.byref(self.buf), self._stream()), name)
+
+    def clear(self):
+        """empty accumulators and histogram, the previous velocities = the simulator's current ones (one launch, no sync)"""
+        self._call("go1eval_joint_clear")
+
+    def arm(self, groups, warmup_steps=0):
+        """start a measurement (as Go1Eval.arm): sets the groups, sizes the two tables and clears"""
+        g = torch.as_tensor(groups).to(torch.int32).reshape(-1)
+        assert g.numel() == self.num_envs, (g.numel(), self.num_envs)
+        G = int(g.max()) + 1
+        assert G >= 1, "no environment carries a group id >= 0"
+        self.group.copy_(g)
+        self.cfg.num_groups, self.cfg.warmup_steps = G, int(warmup_steps)
+        self.table = torch.zeros(G, NUM_DOF * NUM_JOINT + 1, NUM_FIELDS, dtype=torch.float64, device=self.device)
+        self.hist_table = torch.zeros(G, NUM_DOF, JOINT_TAU_BINS, JOINT_VEL_BINS, dtype=torch.int64, device=self.device)   # (uint64 on the device)
+        self._refresh()
+        self.clear()
+        self.armed = True
+
+    def accumulate(self):
+        """after a step: fold the step of every joint (one launch, no sync)"""
+        self._call("go1eval_joint_accumulate")
+
+    def disarm(self):
+        self.armed = False
+
+    def reduce(self):
+        """(the result table [G][12 * 10 + 1][NUM_FIELDS], the histogram table [G][12][8][8]) as device tensors (one launch, no sync)"""
+        assert self.table is not None, "arm() first"
+        self._call("go1eval_joint_reduce")
+        return self.table, self.hist_table
+
+    def read(self):
+        """{"metrics": {name: (G, 12, 6) array with the columns FIELD_NAMES, one row per joint of DOF_NAMES}, "groups": (G, 3) array with
+        the columns JOINT_GROUP_FIELDS, "hist": (G, 12, 8, 8) int64 array [group][joint][torque bin][speed bin], "tau_edges", "vel_edges":
+        (12, 9) bin edges, "steps", "resets": (N,) integer arrays, "prev_dof_vel": (12, N) float32, "env_hist": (12, 64, N)}: one launch
+        and the device-to-host copies of the two tables and the state arrays"""
+        table, hist = self.reduce()
+        table = table.cpu().numpy()
+        rows = table[:, :NUM_DOF * NUM_JOINT, :].reshape(-1, NUM_DOF, NUM_JOINT, NUM_FIELDS)
+        out = dict(metrics={name: rows[:, :, m, :].copy() for m, name in enumerate(JOINT_NAMES)},
+                   groups=table[:, NUM_DOF * NUM_JOINT, :len(JOINT_GROUP_FIELDS)].copy(), hist=hist.cpu().numpy(),
+                   tau_edges=np.stack([joint_edges(self.cfg.torque_limit[j]) for j in range(NUM_DOF)]),
+                   vel_edges=np.stack([joint_edges(self.cfg.vel_limit[j]) for j in range(NUM_DOF)]))
+        out.update({("env_hist" if n == "hist" else n): t.cpu().numpy() for n, t in self.state.items()})
         return out

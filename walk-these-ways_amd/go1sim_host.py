@@ -27,6 +27,7 @@ DOF_NAMES = [f"{leg}_{part}_joint" for leg in LEGS for part in ("hip", "thigh", 
 _DOF_LOWER = [-0.802851455917, -1.0471975512, -2.69653369433] * 4
 _DOF_UPPER = [0.802851455917, 4.18879020479, -0.916297857297] * 4
 _DOF_EFFORT = [33.5] * 12
+_DOF_VELOCITY = [50.0, 28.0, 28.0] * 4     # rad/s, the same <limit> elements: the speed scale of the per-joint metrics (go1eval_host.Go1Joints)
 
 COMMAND_KEYS = ["x_vel", "y_vel", "yaw_vel", "body_height", "gait_frequency", "gait_phase", "gait_offset",
                 "gait_bounds", "gait_duration", "footswing_height", "body_pitch", "body_roll", "stance_width",
