@@ -4,7 +4,6 @@ SIMT emulator against that model bit for bit, the environment hooks where there 
 import ctypes
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -12,6 +11,7 @@ import pytest
 import torch
 
 import response_ref as P
+from test_eval_metrics import _build_eval_emu
 
 REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 HEADER = os.path.join(REPO, "include", "go1eval.h")
@@ -258,25 +258,6 @@ def test_model_group_table():
 
 
 # ---- 4. go1eval.hip under the SIMT emulator against the model ------------------------------------------------------------------------------
-def _build_eval_emu():
-    """tests/test_eval_metrics.py::_build_eval_emu restated: go1eval.hip, unmodified, compiled for the host against tests/emu's
-    stand-in hip/hip_runtime.h and fiber scheduler"""
-    import __graft_entry__ as g
-    emu = os.path.join(REPO, "tests", "emu")
-    src = os.path.join(REPO, "walk-these-ways_amd", "csrc", "go1eval.hip")
-    deps = [src, HEADER, os.path.join(emu, "hip", "hip_runtime.h"), os.path.join(emu, "emu_runtime.cpp")]
-    flags = ["-x", "c++", "-std=c++17", "-O1", "-g", "-fPIC", "-shared", "-fopenmp", "-ffp-contract=off", "-Wno-everything"]
-    out = os.path.join(emu, "_build", "libgo1eval_emu.so")
-    want = g.source_hash(deps, flags)
-    if not (os.path.exists(out) and os.path.exists(out + ".stamp") and open(out + ".stamp").read().strip() == want):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        clang = os.environ.get("EMU_CXX", "/opt/rocm/lib/llvm/bin/clang++")
-        subprocess.check_call([clang] + flags + ["-I", emu, "-o", out, src, os.path.join(emu, "emu_runtime.cpp")], cwd=os.path.dirname(src))
-        with open(out + ".stamp", "w") as fh:
-            fh.write(want)
-    return out
-
-
 @pytest.fixture(scope="module")
 def emu():
     import go1eval_host as G

@@ -22,6 +22,13 @@
 // joint_accumulate_kernel / joint_reduce_kernel: per-joint actuator usage: one thread per (joint, environment) in a one-dimensional
 // launch whose blocks each belong to one joint, so the joint's limits are uniform per block and every row access is a contiguous run
 // (the histogram word alone is scattered); metric rows through reduce_metric_row, the histogram by its own uint64 sums.  tests/joint_ref.py.
+//
+// What the six families share is written once, in the first namespace below: Args (a kernel's one argument: config and buffers by
+// value), Row (a row of an SoA buffer at the thread's environment; TraceAt is the trace's), fold and clear_rows (the six
+// accumulators of a metric row), tree_reduce (the fixed binary tree in LDS), group_sums and reduce_metric_row (the strided pass in
+// front of it: sums over a group's members, and a metric row), Once (one fp32 value per member seen as accumulators that folded it
+// once), status_row and values_table_row (the tables of the response and the recovery).  The entry points at the end share
+// has_accumulators, has_table and launch; what a family validates beyond them stays with the family, in the header's order of codes.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -33,15 +40,39 @@ namespace {
 constexpr int ACC_THREADS = 256;
 constexpr int NM = GO1EVAL_NUM_METRICS, NF = GO1EVAL_NUM_FIELDS, RT = GO1EVAL_REDUCE_THREADS;
 
-struct EvalArgs {
-  Go1EvalConfig c;
-  Go1EvalBuffers b;
+// a kernel's one argument: the caller's config and buffers, by value
+template <class C, class B>
+struct Args {
+  C c;
+  B b;
+};
+using EvalArgs = Args<Go1EvalConfig, Go1EvalBuffers>;
+using BehaviourArgs = Args<Go1BehaviourConfig, Go1BehaviourBuffers>;
+using ResponseArgs = Args<Go1ResponseConfig, Go1ResponseBuffers>;
+using PushArgs = Args<Go1PushConfig, Go1PushBuffers>;
+using RecoveryArgs = Args<Go1RecoveryConfig, Go1RecoveryBuffers>;
+using TerrainArgs = Args<Go1TerrainConfig, Go1TerrainBuffers>;
+using JointArgs = Args<Go1JointConfig, Go1JointBuffers>;
+struct TraceArgs {
+  Go1TraceConfig c;
+  Go1TraceBuffers b;
+  int row;
 };
 
-struct BehaviourArgs {
-  Go1BehaviourConfig c;
-  Go1BehaviourBuffers b;
+// row k of an SoA buffer ([k][N]) at environment e
+struct Row {
+  int N, e;
+  __device__ __forceinline__ float operator()(const float* p, int k) const { return p[(size_t)k * N + e]; }
 };
+
+// rows first_row ... first_row + rows - 1 of the accumulators of environment e: nothing folded yet
+template <class Buffers>
+__device__ __forceinline__ void clear_rows(const Buffers& b, int first_row, int rows, int N, int e) {
+  for (int m = 0; m < rows; m++) {
+    const size_t i = (size_t)(first_row + m) * N + e;
+    b.count[i] = 0u; b.nonfinite[i] = 0u; b.sum[i] = 0.0; b.sumsq[i] = 0.0; b.min[i] = INFINITY; b.max[i] = -INFINITY;
+  }
+}
 
 template <class Buffers>
 __device__ __forceinline__ void fold(const Buffers& b, int m, int N, int e, float v) {
@@ -52,6 +83,34 @@ __device__ __forceinline__ void fold(const Buffers& b, int m, int N, int e, floa
   b.sumsq[i] += (double)v * (double)v;
   b.min[i] = fminf(b.min[i], v);
   b.max[i] = fmaxf(b.max[i], v);
+}
+
+// the binary tree of fixed shape over the partial results of a workgroup of RT threads, thread t's in lds[f][t]: sums in rows
+// 0 ... F - 1 and, with MinMax, a minimum in row F and a maximum in row F + 1.  Afterwards lds[f][0] holds the workgroup's.
+template <int F, bool MinMax = false>
+__device__ __forceinline__ void tree_reduce(double (*lds)[RT], int t) {
+  __syncthreads();
+  for (int s = RT / 2; s > 0; s >>= 1) {
+    if (t < s) {
+      for (int f = 0; f < F; f++) lds[f][t] += lds[f][t + s];
+      if (MinMax) { lds[F][t] = fmin(lds[F][t], lds[F][t + s]); lds[F + 1][t] = fmax(lds[F + 1][t], lds[F + 1][t + s]); }
+    }
+    __syncthreads();
+  }
+}
+
+// F sums over the members of group g, by one workgroup of RT threads: thread t adds term(e, a) for the members e = t, t + RT, ...
+// in ascending order, then the tree; lds[f][0] holds sum f
+template <int F, class Term>
+__device__ __forceinline__ void group_sums(const int32_t* group, int g, int N, double (*lds)[RT], Term term) {
+  const int t = (int)threadIdx.x;
+  double a[F] = {};
+  for (int e = t; e < N; e += RT) {
+    if (group[e] != g) continue;
+    term(e, a);
+  }
+  for (int f = 0; f < F; f++) lds[f][t] = a[f];
+  tree_reduce<F>(lds, t);
 }
 
 // one metric row of a result table, by one workgroup of RT threads: thread t combines the group's environments t, t + RT, ... in
@@ -67,14 +126,7 @@ __device__ __forceinline__ void reduce_metric_row(const Buffers& b, int g, int m
     if (b.count[i] > 0u) { a4 = fmin(a4, (double)b.min[i]); a5 = fmax(a5, (double)b.max[i]); }
   }
   lds[0][t] = a0; lds[1][t] = a1; lds[2][t] = a2; lds[3][t] = a3; lds[4][t] = a4; lds[5][t] = a5;
-  __syncthreads();
-  for (int s = RT / 2; s > 0; s >>= 1) {
-    if (t < s) {
-      for (int f = 0; f < 4; f++) lds[f][t] += lds[f][t + s];
-      lds[4][t] = fmin(lds[4][t], lds[4][t + s]); lds[5][t] = fmax(lds[5][t], lds[5][t + s]);
-    }
-    __syncthreads();
-  }
+  tree_reduce<4, true>(lds, t);
   if (t != 0) return;
   const double nan = (double)NAN;
   const double n = lds[0][0];
@@ -82,6 +134,43 @@ __device__ __forceinline__ void reduce_metric_row(const Buffers& b, int g, int m
   const double var = n > 0.0 ? lds[3][0] / n - mean * mean : nan;
   out[GO1EVAL_F_COUNT] = n; out[GO1EVAL_F_MEAN] = mean; out[GO1EVAL_F_STD] = n > 0.0 ? sqrt(fmax(var, 0.0)) : nan;
   out[GO1EVAL_F_MIN] = n > 0.0 ? lds[4][0] : nan; out[GO1EVAL_F_MAX] = n > 0.0 ? lds[5][0] : nan; out[GO1EVAL_F_NONFINITE] = lds[1][0];
+}
+
+// one fp32 value per member, value(i), seen as the accumulators of a member that folded the one value: what reduce_metric_row reads
+template <class V>
+struct Once {
+  struct Count { V v; __device__ uint32_t operator[](size_t i) const { return isfinite(v(i)) ? 1u : 0u; } };
+  struct Nonfinite { V v; __device__ uint32_t operator[](size_t i) const { return isfinite(v(i)) ? 0u : 1u; } };
+  struct Sum { V v; __device__ double operator[](size_t i) const { const float x = v(i); return isfinite(x) ? (double)x : 0.0; } };
+  struct Sumsq { V v; __device__ double operator[](size_t i) const { const float x = v(i); return isfinite(x) ? (double)x * (double)x : 0.0; } };
+  struct Value { V v; __device__ float operator[](size_t i) const { return v(i); } };
+  const int32_t* group;
+  Count count; Nonfinite nonfinite; Sum sum; Sumsq sumsq; Value min, max;
+};
+template <class V>
+__device__ __forceinline__ Once<V> once(const int32_t* group, V v) { return {group, {v}, {v}, {v}, {v}, {v}, {v}}; }
+struct Stored { const float* v; __device__ float operator()(size_t i) const { return v[i]; } };       // values[s][m][K], as written
+
+// the last row of a group of the response, recovery and terrain tables, by one workgroup of RT threads in reduce_metric_row's
+// combination order: members, members with status 0, 1, 2, 3, then 0 (the response knows no status 3: its count is 0)
+template <class Status>
+__device__ __forceinline__ void status_row(const Status* status, const int32_t* group, int g, int K, double (*lds)[RT], double* out) {
+  group_sums<5>(group, g, K, lds, [status](int e, double* a) {
+    const int st = (int)status[e];
+    a[0] += 1.0; a[1] += st == 0 ? 1.0 : 0.0; a[2] += st == 1 ? 1.0 : 0.0; a[3] += st == 2 ? 1.0 : 0.0; a[4] += st == 3 ? 1.0 : 0.0;
+  });
+  if (threadIdx.x != 0) return;
+  for (int f = 0; f < 5; f++) out[f] = lds[f][0];
+  out[5] = 0.0;
+}
+
+// the workgroup's row of a table of `rows` rows per group over values[rows - 1][K] and status[K]: the response's and the recovery's
+template <class Buffers>
+__device__ __forceinline__ void values_table_row(const Buffers& b, int K, int rows, double (*lds)[RT]) {
+  const int g = (int)blockIdx.x / rows, m = (int)blockIdx.x % rows;
+  double* out = b.results + ((size_t)g * rows + m) * NF;
+  if (m != rows - 1) { reduce_metric_row(once(b.group, Stored{b.values}), g, m, K, lds, out); return; }
+  status_row(b.status, b.group, g, K, lds, out);
 }
 
 // ---- the quaternion algebra the behaviour metrics need (xyzw), restated here: this library shares no source with the simulator
@@ -117,6 +206,20 @@ __device__ __forceinline__ void torque_figures(const float* torques, const float
   *tmax = m; *power = (float)psum;
 }
 
+// foot f touches the ground (the vertical force on its body), and whether that is what the gait wants of it: 1 or 0
+__device__ __forceinline__ bool foot_contact(const Row& row, const float* contact_forces, int f) {
+  return row(contact_forces, (4 + 4 * f) * 3 + 2) > (float)GO1EVAL_CONTACT_FORCE;
+}
+__device__ __forceinline__ int contact_match(bool contact, float desired) { return contact == (desired > 0.5f) ? 1 : 0; }
+
+// a foot's term of feet_clearance: how far its height z misses the commanded swing height at its place in the swing phase, squared,
+// counted while the gait wants it in the air
+__device__ __forceinline__ float clearance_miss(float cmd_swing, float index, float desired, float z) {
+  const float swing_phase = 1.0f - fabsf(1.0f - fminf(fmaxf(index * 2.0f - 1.0f, 0.0f), 1.0f) * 2.0f);
+  const float miss = cmd_swing * swing_phase + (float)GO1EVAL_FOOT_RADIUS - z;
+  return miss * miss * (1.0f - desired);
+}
+
 }  // namespace
 
 extern "C" __global__ void __launch_bounds__(ACC_THREADS) eval_clear_kernel(const EvalArgs A) {
@@ -124,10 +227,7 @@ extern "C" __global__ void __launch_bounds__(ACC_THREADS) eval_clear_kernel(cons
   const int e = (int)(blockIdx.x * ACC_THREADS + threadIdx.x);
   if (e >= N) return;
   const Go1EvalBuffers& b = A.b;
-  for (int m = 0; m < NM; m++) {
-    const size_t i = (size_t)m * N + e;
-    b.count[i] = 0u; b.nonfinite[i] = 0u; b.sum[i] = 0.0; b.sumsq[i] = 0.0; b.min[i] = INFINITY; b.max[i] = -INFINITY;
-  }
+  clear_rows(b, 0, NM, N, e);
   b.steps[e] = 0u; b.episodes_terminated[e] = 0u; b.episodes_timed_out[e] = 0u;
 }
 
@@ -168,27 +268,16 @@ extern "C" __global__ void __launch_bounds__(ACC_THREADS) eval_accumulate_kernel
 extern "C" __global__ void __launch_bounds__(RT) eval_reduce_kernel(const EvalArgs A) {
   __shared__ double lds[NF][RT];
   const int N = A.c.num_envs;
-  const int t = (int)threadIdx.x;
   const int g = (int)blockIdx.x / (NM + 1), m = (int)blockIdx.x % (NM + 1);
   const Go1EvalBuffers& b = A.b;
   double* out = b.results + ((size_t)g * (NM + 1) + m) * NF;
   if (m != NM) { reduce_metric_row(b, g, m, N, lds, out); return; }
-  // the group's own row: a0 envs, a1 steps, a2 terminated, a3 timed out, a4 fallen envs
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = 0.0;
-  for (int e = t; e < N; e += RT) {
-    if (b.group[e] != g) continue;
-    a0 += 1.0; a1 += (double)b.steps[e]; a2 += (double)b.episodes_terminated[e]; a3 += (double)b.episodes_timed_out[e];
-    a4 += b.episodes_terminated[e] > 0u ? 1.0 : 0.0;
-  }
-  lds[0][t] = a0; lds[1][t] = a1; lds[2][t] = a2; lds[3][t] = a3; lds[4][t] = a4;
-  __syncthreads();
-  for (int s = RT / 2; s > 0; s >>= 1) {
-    if (t < s) {
-      for (int f = 0; f < 5; f++) lds[f][t] += lds[f][t + s];
-    }
-    __syncthreads();
-  }
-  if (t != 0) return;
+  // the group's own row: a[0] envs, a[1] steps, a[2] terminated, a[3] timed out, a[4] fallen envs
+  group_sums<5>(b.group, g, N, lds, [&b](int e, double* a) {
+    a[0] += 1.0; a[1] += (double)b.steps[e]; a[2] += (double)b.episodes_terminated[e]; a[3] += (double)b.episodes_timed_out[e];
+    a[4] += b.episodes_terminated[e] > 0u ? 1.0 : 0.0;
+  });
+  if (threadIdx.x != 0) return;
   out[GO1EVAL_G_ENVS] = lds[0][0]; out[GO1EVAL_G_STEPS] = lds[1][0]; out[GO1EVAL_G_TERMINATED] = lds[2][0];
   out[GO1EVAL_G_TIMED_OUT] = lds[3][0]; out[GO1EVAL_G_FALL_RATE] = lds[0][0] > 0.0 ? lds[4][0] / lds[0][0] : (double)NAN; out[5] = 0.0;
 }
@@ -201,10 +290,7 @@ extern "C" __global__ void __launch_bounds__(ACC_THREADS) behaviour_clear_kernel
   const int e = (int)(blockIdx.x * ACC_THREADS + threadIdx.x);
   if (e >= N) return;
   const Go1BehaviourBuffers& b = A.b;
-  for (int m = 0; m < NB; m++) {
-    const size_t i = (size_t)m * N + e;
-    b.count[i] = 0u; b.nonfinite[i] = 0u; b.sum[i] = 0.0; b.sumsq[i] = 0.0; b.min[i] = INFINITY; b.max[i] = -INFINITY;
-  }
+  clear_rows(b, 0, NB, N, e);
   for (int f = 0; f < 4; f++) {
     const size_t i = (size_t)f * N + e;
     b.prev_contact[i] = 2; b.stride_steps[i] = -1; b.stance_steps[i] = 0; b.swing_peak[i] = -INFINITY;
@@ -220,7 +306,7 @@ extern "C" __global__ void __launch_bounds__(ACC_THREADS) behaviour_accumulate_k
     for (int f = 0; f < 4; f++) { b.prev_contact[(size_t)f * N + e] = 2; b.stride_steps[(size_t)f * N + e] = -1; }
     return;
   }
-  const auto row = [N, e](const float* p, int k) { return p[(size_t)k * N + e]; };
+  const Row row = {N, e};
   const float cmd_vx = row(b.commands, 0), cmd_yaw = row(b.commands, 2), cmd_height = row(b.commands, 3), cmd_freq = row(b.commands, 4);
   const float cmd_duty = row(b.commands, 8), cmd_swing = row(b.commands, 9), cmd_pitch = row(b.commands, 10), cmd_roll = row(b.commands, 11);
   const float width = A.c.num_commands >= 13 ? row(b.commands, 12) : 0.3f;
@@ -236,15 +322,13 @@ extern "C" __global__ void __launch_bounds__(ACC_THREADS) behaviour_accumulate_k
   const float yaw_z = -qz / yaw_norm, yaw_w = qw / yaw_norm;
   const float half_period = 0.5f / cmd_freq, cmd_vy = cmd_yaw * length / 2;
   for (int f = 0; f < 4; f++) {
-    contact[f] = row(b.contact_forces, (4 + 4 * f) * 3 + 2) > (float)GO1EVAL_CONTACT_FORCE;
+    contact[f] = foot_contact(row, b.contact_forces, f);
     const float desired = row(b.desired_contact_states, f), index = row(b.foot_indices, f);
-    matches += contact[f] == (desired > 0.5f) ? 1 : 0;
+    matches += contact_match(contact[f], desired);
     const V3 pos = {row(b.foot_positions, 3 * f), row(b.foot_positions, 3 * f + 1), row(b.foot_positions, 3 * f + 2)};
     foot_z[f] = pos.z;
 
-    const float swing_phase = 1.0f - fabsf(1.0f - fminf(fmaxf(index * 2.0f - 1.0f, 0.0f), 1.0f) * 2.0f);
-    const float miss = cmd_swing * swing_phase + (float)GO1EVAL_FOOT_RADIUS - pos.z;
-    clearance += (double)(miss * miss * (1.0f - desired));
+    clearance += (double)clearance_miss(cmd_swing, index, desired, pos.z);
 
     const V3 rel = quat_rotate(0.0f, 0.0f, yaw_z, yaw_w, V3{pos.x - base.x, pos.y - base.y, pos.z - base.z});
     const float xs = (f < 2 ? 1.0f : -1.0f) * length / 2, ys = (f % 2 == 0 ? 1.0f : -1.0f) * width / 2;
@@ -313,16 +397,13 @@ extern "C" __global__ void __launch_bounds__(RT) behaviour_reduce_kernel(const B
 // ---- the trace and the step response --------------------------------------------------------------------------------------------
 constexpr int NT = GO1EVAL_NUM_TRACE, NR = GO1EVAL_NUM_RESPONSE;
 
-struct TraceArgs {
-  Go1TraceConfig c;
-  Go1TraceBuffers b;
-  int row;
+namespace {
+// channel ch of row t of the trace at traced environment k: consecutive k, consecutive floats
+struct TraceAt {
+  const float* trace; int K, k;
+  __device__ __forceinline__ float operator()(int t, int ch) const { return trace[((size_t)t * NT + ch) * K + k]; }
 };
-
-struct ResponseArgs {
-  Go1ResponseConfig c;
-  Go1ResponseBuffers b;
-};
+}  // namespace
 
 extern "C" __global__ void __launch_bounds__(ACC_THREADS) trace_record_kernel(const TraceArgs A) {
   const int N = A.c.num_envs, K = A.c.num_traced;
@@ -335,15 +416,14 @@ extern "C" __global__ void __launch_bounds__(ACC_THREADS) trace_record_kernel(co
     for (int c = 0; c < NT; c++) out[(size_t)c * K] = NAN;
     return;
   }
-  const auto row = [N, e](const float* p, int r) { return p[(size_t)r * N + e]; };
+  const Row row = {N, e};
   out[(size_t)GO1TRACE_LIN_VEL_X * K] = row(b.base_lin_vel, 0);
   out[(size_t)GO1TRACE_LIN_VEL_Y * K] = row(b.base_lin_vel, 1);
   out[(size_t)GO1TRACE_ANG_VEL_YAW * K] = row(b.base_ang_vel, 2);
   out[(size_t)GO1TRACE_BASE_HEIGHT * K] = height_above_ground(b.measured_heights, A.c.num_height_points, N, e, row(b.root_states, 2));
   int matches = 0;
   for (int f = 0; f < 4; f++) {
-    const bool contact = row(b.contact_forces, (4 + 4 * f) * 3 + 2) > (float)GO1EVAL_CONTACT_FORCE;
-    matches += contact == (row(b.desired_contact_states, f) > 0.5f) ? 1 : 0;
+    matches += contact_match(foot_contact(row, b.contact_forces, f), row(b.desired_contact_states, f));
   }
   out[(size_t)GO1TRACE_CONTACT_MATCH * K] = 0.25f * (float)matches;
   float tmax, power;
@@ -363,8 +443,7 @@ extern "C" __global__ void __launch_bounds__(ACC_THREADS) response_kernel(const 
   const int K = c.num_traced;
   const int k = (int)(blockIdx.x * ACC_THREADS + threadIdx.x);
   if (k >= K) return;
-  const float* trace = A.b.trace;
-  const auto at = [trace, K, k](int t, int ch) { return trace[((size_t)t * NT + ch) * K + k]; };   // consecutive k, consecutive floats
+  const TraceAt at = {A.b.trace, K, k};
   const int s0 = c.switch_row, end = c.rows, w = c.smooth;
 
   int status = 0;
@@ -421,70 +500,13 @@ extern "C" __global__ void __launch_bounds__(ACC_THREADS) response_kernel(const 
   }
 }
 
-namespace {
-// values[s][m][K] seen as the accumulators of an environment that folded the one value: what reduce_metric_row reads
-struct FoldedOnce {
-  struct Count { const float* v; __device__ uint32_t operator[](size_t i) const { return isfinite(v[i]) ? 1u : 0u; } };
-  struct Nonfinite { const float* v; __device__ uint32_t operator[](size_t i) const { return isfinite(v[i]) ? 0u : 1u; } };
-  struct Sum { const float* v; __device__ double operator[](size_t i) const { return isfinite(v[i]) ? (double)v[i] : 0.0; } };
-  struct Sumsq { const float* v; __device__ double operator[](size_t i) const { return isfinite(v[i]) ? (double)v[i] * (double)v[i] : 0.0; } };
-  struct Value { const float* v; __device__ float operator[](size_t i) const { return v[i]; } };
-  const int32_t* group;
-  Count count; Nonfinite nonfinite; Sum sum; Sumsq sumsq; Value min, max;
-};
-
-// the last row of a group of the response and recovery tables, by one workgroup of RT threads in reduce_metric_row's combination
-// order: traced environments, environments with status 0, 1, 2, 3, then 0 (the response knows no status 3: its count is 0)
-template <class Status>
-__device__ __forceinline__ void status_row(const Status* status, const int32_t* group, int g, int K, double (*lds)[RT], double* out) {
-  const int t = (int)threadIdx.x;
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = 0.0;
-  for (int e = t; e < K; e += RT) {
-    if (group[e] != g) continue;
-    const int st = (int)status[e];
-    a0 += 1.0; a1 += st == 0 ? 1.0 : 0.0; a2 += st == 1 ? 1.0 : 0.0; a3 += st == 2 ? 1.0 : 0.0; a4 += st == 3 ? 1.0 : 0.0;
-  }
-  lds[0][t] = a0; lds[1][t] = a1; lds[2][t] = a2; lds[3][t] = a3; lds[4][t] = a4;
-  __syncthreads();
-  for (int s = RT / 2; s > 0; s >>= 1) {
-    if (t < s) {
-      for (int f = 0; f < 5; f++) lds[f][t] += lds[f][t + s];
-    }
-    __syncthreads();
-  }
-  if (t != 0) return;
-  for (int f = 0; f < 5; f++) out[f] = lds[f][0];
-  out[5] = 0.0;
-}
-}  // namespace
-
 extern "C" __global__ void __launch_bounds__(RT) response_reduce_kernel(const ResponseArgs A) {
   __shared__ double lds[NF][RT];
-  const int K = A.c.num_traced, rows = A.c.num_signals * NR + 1;
-  const int g = (int)blockIdx.x / rows, m = (int)blockIdx.x % rows;
-  const Go1ResponseBuffers& b = A.b;
-  double* out = b.results + ((size_t)g * rows + m) * NF;
-  if (m != rows - 1) {
-    const float* v = b.values;
-    const FoldedOnce once = {b.group, {v}, {v}, {v}, {v}, {v}, {v}};
-    reduce_metric_row(once, g, m, K, lds, out);
-    return;
-  }
-  status_row(b.status, b.group, g, K, lds, out);
+  values_table_row(A.b, A.c.num_traced, A.c.num_signals * NR + 1, lds);
 }
 
 // ---- the push and the disturbance recovery --------------------------------------------------------------------------------------
 constexpr int NV = GO1EVAL_NUM_RECOVERY;
-
-struct PushArgs {
-  Go1PushConfig c;
-  Go1PushBuffers b;
-};
-
-struct RecoveryArgs {
-  Go1RecoveryConfig c;
-  Go1RecoveryBuffers b;
-};
 
 extern "C" __global__ void __launch_bounds__(ACC_THREADS) push_kernel(const PushArgs A) {
   const int N = A.c.num_envs, K = A.c.num_pushed;
@@ -512,8 +534,7 @@ extern "C" __global__ void __launch_bounds__(ACC_THREADS) recovery_kernel(const 
   const int K = c.num_traced;
   const int k = (int)(blockIdx.x * ACC_THREADS + threadIdx.x);
   if (k >= K) return;
-  const float* trace = A.b.trace;
-  const auto at = [trace, K, k](int t, int ch) { return trace[((size_t)t * NT + ch) * K + k]; };   // consecutive k, consecutive floats
+  const TraceAt at = {A.b.trace, K, k};
   const int p0 = c.push_row, first = c.push_row - c.pre, end = c.rows, w = c.smooth;
 
   bool spoiled = false, fell = false, moved = false;
@@ -571,26 +592,11 @@ extern "C" __global__ void __launch_bounds__(ACC_THREADS) recovery_kernel(const 
 
 extern "C" __global__ void __launch_bounds__(RT) recovery_reduce_kernel(const RecoveryArgs A) {
   __shared__ double lds[NF][RT];
-  const int K = A.c.num_traced;
-  const int g = (int)blockIdx.x / (NV + 1), m = (int)blockIdx.x % (NV + 1);
-  const Go1RecoveryBuffers& b = A.b;
-  double* out = b.results + ((size_t)g * (NV + 1) + m) * NF;
-  if (m != NV) {
-    const float* v = b.values;
-    const FoldedOnce once = {b.group, {v}, {v}, {v}, {v}, {v}, {v}};
-    reduce_metric_row(once, g, m, K, lds, out);
-    return;
-  }
-  status_row(b.status, b.group, g, K, lds, out);
+  values_table_row(A.b, A.c.num_traced, NV + 1, lds);
 }
 
 // ---- terrain traversal ----------------------------------------------------------------------------------------------------------
 constexpr int NTM = GO1EVAL_NUM_TERRAIN, NTO = GO1EVAL_NUM_OUTCOME;
-
-struct TerrainArgs {
-  Go1TerrainConfig c;
-  Go1TerrainBuffers b;
-};
 
 namespace {
 // where the three samples under world (x, y) start: the truncated index, clamped in fp32 before the conversion (see the header).
@@ -606,7 +612,7 @@ __device__ __forceinline__ Cell cell_under(const Go1TerrainConfig& c, bool field
   return {cell_index(x, c.hf_border, c.hf_hscale, c.hf_rows) * c.hf_cols + cell_index(y, c.hf_border, c.hf_hscale, c.hf_cols), true};
 }
 
-// one fp32 value per environment seen as the accumulators of an environment that folded it once (FoldedOnce, over a computed value)
+// outcome `which` of environment e, computed from its state: what Once reads in place of a stored value
 struct TerrainOutcome {
   const uint8_t* status; const uint32_t* end_step; const float* max_dist; float dt; int which;
   __device__ float operator()(size_t e) const {
@@ -619,15 +625,6 @@ struct TerrainOutcome {
     }
   }
 };
-struct OutcomeOnce {
-  struct Count { TerrainOutcome v; __device__ uint32_t operator[](size_t i) const { return isfinite(v(i)) ? 1u : 0u; } };
-  struct Nonfinite { TerrainOutcome v; __device__ uint32_t operator[](size_t i) const { return isfinite(v(i)) ? 0u : 1u; } };
-  struct Sum { TerrainOutcome v; __device__ double operator[](size_t i) const { const float x = v(i); return isfinite(x) ? (double)x : 0.0; } };
-  struct Sumsq { TerrainOutcome v; __device__ double operator[](size_t i) const { const float x = v(i); return isfinite(x) ? (double)x * (double)x : 0.0; } };
-  struct Value { TerrainOutcome v; __device__ float operator[](size_t i) const { return v(i); } };
-  const int32_t* group;
-  Count count; Nonfinite nonfinite; Sum sum; Sumsq sumsq; Value min, max;
-};
 }  // namespace
 
 extern "C" __global__ void __launch_bounds__(ACC_THREADS) terrain_clear_kernel(const TerrainArgs A) {
@@ -635,10 +632,7 @@ extern "C" __global__ void __launch_bounds__(ACC_THREADS) terrain_clear_kernel(c
   const int e = (int)(blockIdx.x * ACC_THREADS + threadIdx.x);
   if (e >= N) return;
   const Go1TerrainBuffers& b = A.b;
-  for (int m = 0; m < NTM; m++) {
-    const size_t i = (size_t)m * N + e;
-    b.count[i] = 0u; b.nonfinite[i] = 0u; b.sum[i] = 0.0; b.sumsq[i] = 0.0; b.min[i] = INFINITY; b.max[i] = -INFINITY;
-  }
+  clear_rows(b, 0, NTM, N, e);
   b.status[e] = GO1TERRAIN_S_RUNNING; b.steps[e] = 0u; b.end_step[e] = 0u; b.max_dist[e] = 0.0f;
 }
 
@@ -654,7 +648,7 @@ extern "C" __global__ void __launch_bounds__(ACC_THREADS) terrain_accumulate_ker
     b.end_step[e] = b.steps[e] + 1u;
     return;
   }
-  const auto row = [N, e](const float* p, int k) { return p[(size_t)k * N + e]; };
+  const Row row = {N, e};
   const uint32_t steps = b.steps[e] + 1u;
   b.steps[e] = steps;
   const V3 base = {row(b.root_states, 0), row(b.root_states, 1), row(b.root_states, 2)};
@@ -693,9 +687,7 @@ extern "C" __global__ void __launch_bounds__(ACC_THREADS) terrain_accumulate_ker
   bool stumble = false;
   for (int f = 0; f < 4; f++) {
     const float desired = row(b.desired_contact_states, f), index = row(b.foot_indices, f), a = above[1 + f];
-    const float swing_phase = 1.0f - fabsf(1.0f - fminf(fmaxf(index * 2.0f - 1.0f, 0.0f), 1.0f) * 2.0f);
-    const float miss = cmd_swing * swing_phase + (float)GO1EVAL_FOOT_RADIUS - a;
-    clearance += (double)(miss * miss * (1.0f - desired));
+    clearance += (double)clearance_miss(cmd_swing, index, desired, a);
     if (desired <= 0.5f) { swing += (double)(a - (float)GO1EVAL_FOOT_RADIUS); swinging += 1; }
     const int body = 4 + 4 * f;
     const float fx = row(b.contact_forces, 3 * body), fy = row(b.contact_forces, 3 * body + 1), fz = row(b.contact_forces, 3 * body + 2);
@@ -724,8 +716,7 @@ extern "C" __global__ void __launch_bounds__(RT) terrain_reduce_kernel(const Ter
   if (m < NTM) { reduce_metric_row(b, g, m, N, lds, out); return; }
   if (m < NTM + NTO) {
     const TerrainOutcome v = {b.status, b.end_step, b.max_dist, A.c.dt, m - NTM};
-    const OutcomeOnce once = {b.group, {v}, {v}, {v}, {v}, {v}, {v}};
-    reduce_metric_row(once, g, 0, N, lds, out);                  // (row 0 of a table of one row: index e)
+    reduce_metric_row(once(b.group, v), g, 0, N, lds, out);      // (row 0 of a table of one row: index e)
     return;
   }
   status_row(b.status, b.group, g, N, lds, out);                 // environments, status 0, 1, 2, 3
@@ -737,11 +728,6 @@ extern "C" __global__ void __launch_bounds__(RT) terrain_reduce_kernel(const Ter
 // ---- per-joint actuator usage ---------------------------------------------------------------------------------------------------
 constexpr int NJ = GO1EVAL_NUM_JOINT, DOF = 12, TB = GO1JOINT_TAU_BINS, VB = GO1JOINT_VEL_BINS, CELLS = TB * VB;
 static_assert(RT == 4 * CELLS, "joint_reduce_kernel: four slices of environments per histogram cell");
-
-struct JointArgs {
-  Go1JointConfig c;
-  Go1JointBuffers b;
-};
 
 namespace {
 // the histogram bin of x on the scale L: clamped as a float, then converted (see the header)
@@ -763,10 +749,7 @@ extern "C" __global__ void __launch_bounds__(ACC_THREADS) joint_clear_kernel(con
   int j, e;
   if (!joint_thread(N, &j, &e)) return;
   const Go1JointBuffers& b = A.b;
-  for (int m = 0; m < NJ; m++) {
-    const size_t i = (size_t)(j * NJ + m) * N + e;
-    b.count[i] = 0u; b.nonfinite[i] = 0u; b.sum[i] = 0.0; b.sumsq[i] = 0.0; b.min[i] = INFINITY; b.max[i] = -INFINITY;
-  }
+  clear_rows(b, j * NJ, NJ, N, e);
   for (int cell = 0; cell < CELLS; cell++) b.hist[(size_t)(j * CELLS + cell) * N + e] = 0u;
   b.prev_dof_vel[(size_t)j * N + e] = b.dof_vel[(size_t)j * N + e];
   if (j == 0) { b.steps[e] = 0u; b.resets[e] = 0u; }
@@ -822,20 +805,8 @@ extern "C" __global__ void __launch_bounds__(RT) joint_reduce_kernel(const Joint
     const int g = (int)blockIdx.x / rows, m = (int)blockIdx.x % rows;
     double* out = b.results + ((size_t)g * rows + m) * NF;
     if (m != rows - 1) { reduce_metric_row(b, g, m, N, lds, out); return; }
-    // the group's own row: a0 envs, a1 steps, a2 resets
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-    for (int e = t; e < N; e += RT) {
-      if (b.group[e] != g) continue;
-      a0 += 1.0; a1 += (double)b.steps[e]; a2 += (double)b.resets[e];
-    }
-    lds[0][t] = a0; lds[1][t] = a1; lds[2][t] = a2;
-    __syncthreads();
-    for (int s = RT / 2; s > 0; s >>= 1) {
-      if (t < s) {
-        for (int f = 0; f < 3; f++) lds[f][t] += lds[f][t + s];
-      }
-      __syncthreads();
-    }
+    // the group's own row: a[0] envs, a[1] steps, a[2] resets
+    group_sums<3>(b.group, g, N, lds, [&b](int e, double* a) { a[0] += 1.0; a[1] += (double)b.steps[e]; a[2] += (double)b.resets[e]; });
     if (t != 0) return;
     out[GO1JOINT_G_ENVS] = lds[0][0]; out[GO1JOINT_G_STEPS] = lds[1][0]; out[GO1JOINT_G_RESETS] = lds[2][0];
     out[3] = 0.0; out[4] = 0.0; out[5] = 0.0;
@@ -856,57 +827,84 @@ extern "C" __global__ void __launch_bounds__(RT) joint_reduce_kernel(const Joint
   if (t < CELLS) b.hist_results[((size_t)g * DOF + j) * CELLS + t] = cells[t] + cells[t + CELLS];
 }
 
+// ---- the entry points: validation in the order the header gives the codes, then one launch -------------------------------------------
 namespace {
+dim3 env_grid(int n) { return dim3((unsigned)((n + ACC_THREADS - 1) / ACC_THREADS)); }
+dim3 joint_grid(int n) { return dim3((unsigned)(DOF * ((n + ACC_THREADS - 1) / ACC_THREADS))); }
+dim3 table_grid(int groups, int rows) { return dim3((unsigned)(groups * rows)); }
+
+template <class A>
+int launch_args(void (*kernel)(A), dim3 grid, int block, void* stream, const A& args) {
+  hipLaunchKernelGGL(kernel, grid, dim3(block), 0, (hipStream_t)stream, args);
+  return hipGetLastError() == hipSuccess ? 0 : -20;
+}
+template <class C, class B>
+int launch(void (*kernel)(Args<C, B>), dim3 grid, int block, void* stream, const C* cfg, const B* buf) {
+  Args<C, B> A; A.c = *cfg; A.b = *buf;
+  return launch_args(kernel, grid, block, stream, A);
+}
+
+template <class B> bool has_accumulators(const B* buf) { return buf->count && buf->sum && buf->sumsq && buf->min && buf->max && buf->nonfinite; }
+template <class C, class B> bool has_table(const C* cfg, const B* buf) { return cfg->num_groups > 0 && buf->group && buf->results; }      // else -5
+template <class C, class B> bool heights_without_points(const C* cfg, const B* buf) { return buf->measured_heights && cfg->num_height_points <= 0; }   // -4
+bool positive(float x) { return x > 0.0f && x <= 3.402823466e38f; }            // finite and positive (a NaN fails both)
+
+// what every entry point of a family asks first: -1, -2 (and the response's -10 for a signal count outside the config's array)
 int check(const Go1EvalConfig* cfg, const Go1EvalBuffers* buf) {
   if (!cfg || !buf || cfg->num_envs <= 0) return -1;
-  if (!buf->count || !buf->sum || !buf->sumsq || !buf->min || !buf->max || !buf->nonfinite || !buf->steps || !buf->episodes_terminated ||
-      !buf->episodes_timed_out) return -2;
+  if (!has_accumulators(buf) || !buf->steps || !buf->episodes_terminated || !buf->episodes_timed_out) return -2;
   return 0;
 }
-EvalArgs args_of(const Go1EvalConfig* cfg, const Go1EvalBuffers* buf) { EvalArgs A; A.c = *cfg; A.b = *buf; return A; }
-dim3 env_grid(int n) { return dim3((unsigned)((n + ACC_THREADS - 1) / ACC_THREADS)); }
+int check(const Go1BehaviourConfig* cfg, const Go1BehaviourBuffers* buf) {
+  if (!cfg || !buf || cfg->num_envs <= 0) return -1;
+  if (!has_accumulators(buf) || !buf->prev_contact || !buf->stride_steps || !buf->stance_steps || !buf->swing_peak) return -2;
+  return 0;
+}
+int check(const Go1ResponseConfig* cfg, const Go1ResponseBuffers* buf) {
+  if (!cfg || !buf || cfg->num_traced <= 0) return -1;
+  if (!buf->values || !buf->status) return -2;
+  if (cfg->num_signals < 1 || cfg->num_signals > GO1EVAL_MAX_SIGNALS) return -10;
+  return 0;
+}
+int check(const Go1RecoveryConfig* cfg, const Go1RecoveryBuffers* buf) {
+  if (!cfg || !buf || cfg->num_traced <= 0) return -1;
+  if (!buf->values || !buf->status) return -2;
+  return 0;
+}
+int check(const Go1TerrainConfig* cfg, const Go1TerrainBuffers* buf) {
+  if (!cfg || !buf || cfg->num_envs <= 0) return -1;
+  if (!has_accumulators(buf) || !buf->status || !buf->steps || !buf->end_step || !buf->max_dist) return -2;
+  return 0;
+}
+int check(const Go1JointConfig* cfg, const Go1JointBuffers* buf) {
+  if (!cfg || !buf || cfg->num_envs <= 0) return -1;
+  if (!has_accumulators(buf) || !buf->prev_dof_vel || !buf->steps || !buf->resets || !buf->hist) return -2;
+  return 0;
+}
 }  // namespace
 
 extern "C" int go1eval_clear(const Go1EvalConfig* cfg, const Go1EvalBuffers* buf, void* stream) {
   if (int rc = check(cfg, buf)) return rc;
-  const EvalArgs A = args_of(cfg, buf);
-  hipLaunchKernelGGL(eval_clear_kernel, env_grid(cfg->num_envs), dim3(ACC_THREADS), 0, (hipStream_t)stream, A);
-  return hipGetLastError() == hipSuccess ? 0 : -20;
+  return launch(eval_clear_kernel, env_grid(cfg->num_envs), ACC_THREADS, stream, cfg, buf);
 }
 
 extern "C" int go1eval_accumulate(const Go1EvalConfig* cfg, const Go1EvalBuffers* buf, void* stream) {
   if (int rc = check(cfg, buf)) return rc;
   if (!buf->base_lin_vel || !buf->base_ang_vel || !buf->commands || !buf->root_states || !buf->torques || !buf->dof_vel || !buf->payloads ||
       !buf->reset_buf || !buf->time_out_buf || !buf->episode_length_buf) return -3;
-  if (buf->measured_heights && cfg->num_height_points <= 0) return -4;
-  const EvalArgs A = args_of(cfg, buf);
-  hipLaunchKernelGGL(eval_accumulate_kernel, env_grid(cfg->num_envs), dim3(ACC_THREADS), 0, (hipStream_t)stream, A);
-  return hipGetLastError() == hipSuccess ? 0 : -20;
+  if (heights_without_points(cfg, buf)) return -4;
+  return launch(eval_accumulate_kernel, env_grid(cfg->num_envs), ACC_THREADS, stream, cfg, buf);
 }
 
 extern "C" int go1eval_reduce(const Go1EvalConfig* cfg, const Go1EvalBuffers* buf, void* stream) {
   if (int rc = check(cfg, buf)) return rc;
-  if (cfg->num_groups <= 0 || !buf->group || !buf->results) return -5;
-  const EvalArgs A = args_of(cfg, buf);
-  hipLaunchKernelGGL(eval_reduce_kernel, dim3((unsigned)(cfg->num_groups * (NM + 1))), dim3(RT), 0, (hipStream_t)stream, A);
-  return hipGetLastError() == hipSuccess ? 0 : -20;
+  if (!has_table(cfg, buf)) return -5;
+  return launch(eval_reduce_kernel, table_grid(cfg->num_groups, NM + 1), RT, stream, cfg, buf);
 }
-
-namespace {
-int check(const Go1BehaviourConfig* cfg, const Go1BehaviourBuffers* buf) {
-  if (!cfg || !buf || cfg->num_envs <= 0) return -1;
-  if (!buf->count || !buf->sum || !buf->sumsq || !buf->min || !buf->max || !buf->nonfinite || !buf->prev_contact || !buf->stride_steps ||
-      !buf->stance_steps || !buf->swing_peak) return -2;
-  return 0;
-}
-BehaviourArgs args_of(const Go1BehaviourConfig* cfg, const Go1BehaviourBuffers* buf) { BehaviourArgs A; A.c = *cfg; A.b = *buf; return A; }
-}  // namespace
 
 extern "C" int go1eval_behaviour_clear(const Go1BehaviourConfig* cfg, const Go1BehaviourBuffers* buf, void* stream) {
   if (int rc = check(cfg, buf)) return rc;
-  const BehaviourArgs A = args_of(cfg, buf);
-  hipLaunchKernelGGL(behaviour_clear_kernel, env_grid(cfg->num_envs), dim3(ACC_THREADS), 0, (hipStream_t)stream, A);
-  return hipGetLastError() == hipSuccess ? 0 : -20;
+  return launch(behaviour_clear_kernel, env_grid(cfg->num_envs), ACC_THREADS, stream, cfg, buf);
 }
 
 extern "C" int go1eval_behaviour_accumulate(const Go1BehaviourConfig* cfg, const Go1BehaviourBuffers* buf, void* stream) {
@@ -914,19 +912,15 @@ extern "C" int go1eval_behaviour_accumulate(const Go1BehaviourConfig* cfg, const
   if (!buf->commands || !buf->root_states || !buf->contact_forces || !buf->foot_positions || !buf->foot_velocities ||
       !buf->desired_contact_states || !buf->foot_indices || !buf->last_actions || !buf->last_last_actions || !buf->reset_buf ||
       !buf->episode_length_buf) return -3;
-  if (buf->measured_heights && cfg->num_height_points <= 0) return -4;
+  if (heights_without_points(cfg, buf)) return -4;
   if (cfg->num_commands < 12 || !(cfg->dt > 0.0f)) return -6;
-  const BehaviourArgs A = args_of(cfg, buf);
-  hipLaunchKernelGGL(behaviour_accumulate_kernel, env_grid(cfg->num_envs), dim3(ACC_THREADS), 0, (hipStream_t)stream, A);
-  return hipGetLastError() == hipSuccess ? 0 : -20;
+  return launch(behaviour_accumulate_kernel, env_grid(cfg->num_envs), ACC_THREADS, stream, cfg, buf);
 }
 
 extern "C" int go1eval_behaviour_reduce(const Go1BehaviourConfig* cfg, const Go1BehaviourBuffers* buf, void* stream) {
   if (int rc = check(cfg, buf)) return rc;
-  if (cfg->num_groups <= 0 || !buf->group || !buf->results) return -5;
-  const BehaviourArgs A = args_of(cfg, buf);
-  hipLaunchKernelGGL(behaviour_reduce_kernel, dim3((unsigned)(cfg->num_groups * NB)), dim3(RT), 0, (hipStream_t)stream, A);
-  return hipGetLastError() == hipSuccess ? 0 : -20;
+  if (!has_table(cfg, buf)) return -5;
+  return launch(behaviour_reduce_kernel, table_grid(cfg->num_groups, NB), RT, stream, cfg, buf);
 }
 
 extern "C" int go1eval_trace_record(const Go1TraceConfig* cfg, const Go1TraceBuffers* buf, int32_t row, void* stream) {
@@ -934,23 +928,12 @@ extern "C" int go1eval_trace_record(const Go1TraceConfig* cfg, const Go1TraceBuf
   if (cfg->num_traced <= 0 || cfg->capacity <= 0 || !buf->trace) return -2;
   if (!buf->base_lin_vel || !buf->base_ang_vel || !buf->commands || !buf->root_states || !buf->contact_forces ||
       !buf->desired_contact_states || !buf->torques || !buf->dof_vel || !buf->dof_pos || !buf->reset_buf) return -3;
-  if (buf->measured_heights && cfg->num_height_points <= 0) return -4;
+  if (heights_without_points(cfg, buf)) return -4;
   if (!buf->env_ids && cfg->num_traced != cfg->num_envs) return -8;
   if (row < 0 || row >= cfg->capacity) return -7;
   TraceArgs A; A.c = *cfg; A.b = *buf; A.row = row;
-  hipLaunchKernelGGL(trace_record_kernel, env_grid(cfg->num_traced), dim3(ACC_THREADS), 0, (hipStream_t)stream, A);
-  return hipGetLastError() == hipSuccess ? 0 : -20;
+  return launch_args(trace_record_kernel, env_grid(cfg->num_traced), ACC_THREADS, stream, A);
 }
-
-namespace {
-int check(const Go1ResponseConfig* cfg, const Go1ResponseBuffers* buf) {
-  if (!cfg || !buf || cfg->num_traced <= 0) return -1;
-  if (!buf->values || !buf->status) return -2;
-  if (cfg->num_signals < 1 || cfg->num_signals > GO1EVAL_MAX_SIGNALS) return -10;
-  return 0;
-}
-ResponseArgs args_of(const Go1ResponseConfig* cfg, const Go1ResponseBuffers* buf) { ResponseArgs A; A.c = *cfg; A.b = *buf; return A; }
-}  // namespace
 
 extern "C" int go1eval_response(const Go1ResponseConfig* cfg, const Go1ResponseBuffers* buf, void* stream) {
   if (int rc = check(cfg, buf)) return rc;
@@ -962,36 +945,21 @@ extern "C" int go1eval_response(const Go1ResponseConfig* cfg, const Go1ResponseB
     const Go1ResponseSignal& g = cfg->signal[s];
     if (g.y_channel < 0 || g.y_channel >= NT || g.r_channel >= NT) return -10;
   }
-  const ResponseArgs A = args_of(cfg, buf);
-  hipLaunchKernelGGL(response_kernel, env_grid(cfg->num_traced), dim3(ACC_THREADS), 0, (hipStream_t)stream, A);
-  return hipGetLastError() == hipSuccess ? 0 : -20;
+  return launch(response_kernel, env_grid(cfg->num_traced), ACC_THREADS, stream, cfg, buf);
 }
 
 extern "C" int go1eval_response_reduce(const Go1ResponseConfig* cfg, const Go1ResponseBuffers* buf, void* stream) {
   if (int rc = check(cfg, buf)) return rc;
-  if (cfg->num_groups <= 0 || !buf->group || !buf->results) return -5;
-  const ResponseArgs A = args_of(cfg, buf);
-  hipLaunchKernelGGL(response_reduce_kernel, dim3((unsigned)(cfg->num_groups * (cfg->num_signals * NR + 1))), dim3(RT), 0, (hipStream_t)stream, A);
-  return hipGetLastError() == hipSuccess ? 0 : -20;
+  if (!has_table(cfg, buf)) return -5;
+  return launch(response_reduce_kernel, table_grid(cfg->num_groups, cfg->num_signals * NR + 1), RT, stream, cfg, buf);
 }
 
 extern "C" int go1eval_push(const Go1PushConfig* cfg, const Go1PushBuffers* buf, void* stream) {
   if (!cfg || !buf || cfg->num_envs <= 0) return -1;
   if (cfg->num_pushed <= 0 || !buf->root_states || !buf->push) return -2;
   if (!buf->env_ids && cfg->num_pushed != cfg->num_envs) return -8;
-  PushArgs A; A.c = *cfg; A.b = *buf;
-  hipLaunchKernelGGL(push_kernel, env_grid(cfg->num_pushed), dim3(ACC_THREADS), 0, (hipStream_t)stream, A);
-  return hipGetLastError() == hipSuccess ? 0 : -20;
+  return launch(push_kernel, env_grid(cfg->num_pushed), ACC_THREADS, stream, cfg, buf);
 }
-
-namespace {
-int check(const Go1RecoveryConfig* cfg, const Go1RecoveryBuffers* buf) {
-  if (!cfg || !buf || cfg->num_traced <= 0) return -1;
-  if (!buf->values || !buf->status) return -2;
-  return 0;
-}
-RecoveryArgs args_of(const Go1RecoveryConfig* cfg, const Go1RecoveryBuffers* buf) { RecoveryArgs A; A.c = *cfg; A.b = *buf; return A; }
-}  // namespace
 
 extern "C" int go1eval_recovery(const Go1RecoveryConfig* cfg, const Go1RecoveryBuffers* buf, void* stream) {
   if (int rc = check(cfg, buf)) return rc;
@@ -999,34 +967,18 @@ extern "C" int go1eval_recovery(const Go1RecoveryConfig* cfg, const Go1RecoveryB
   const int w = cfg->smooth, p0 = cfg->push_row, rows = cfg->rows;
   if (!(1 <= cfg->pre && cfg->pre <= p0 && p0 < rows && 1 <= w && w <= cfg->pre + 1 && 1 <= cfg->hold && cfg->hold <= rows - p0 &&
         cfg->dt > 0.0f && cfg->band >= 0.0f)) return -11;
-  const RecoveryArgs A = args_of(cfg, buf);
-  hipLaunchKernelGGL(recovery_kernel, env_grid(cfg->num_traced), dim3(ACC_THREADS), 0, (hipStream_t)stream, A);
-  return hipGetLastError() == hipSuccess ? 0 : -20;
+  return launch(recovery_kernel, env_grid(cfg->num_traced), ACC_THREADS, stream, cfg, buf);
 }
 
 extern "C" int go1eval_recovery_reduce(const Go1RecoveryConfig* cfg, const Go1RecoveryBuffers* buf, void* stream) {
   if (int rc = check(cfg, buf)) return rc;
-  if (cfg->num_groups <= 0 || !buf->group || !buf->results) return -5;
-  const RecoveryArgs A = args_of(cfg, buf);
-  hipLaunchKernelGGL(recovery_reduce_kernel, dim3((unsigned)(cfg->num_groups * (NV + 1))), dim3(RT), 0, (hipStream_t)stream, A);
-  return hipGetLastError() == hipSuccess ? 0 : -20;
+  if (!has_table(cfg, buf)) return -5;
+  return launch(recovery_reduce_kernel, table_grid(cfg->num_groups, NV + 1), RT, stream, cfg, buf);
 }
-
-namespace {
-int check(const Go1TerrainConfig* cfg, const Go1TerrainBuffers* buf) {
-  if (!cfg || !buf || cfg->num_envs <= 0) return -1;
-  if (!buf->count || !buf->sum || !buf->sumsq || !buf->min || !buf->max || !buf->nonfinite || !buf->status || !buf->steps || !buf->end_step ||
-      !buf->max_dist) return -2;
-  return 0;
-}
-TerrainArgs args_of(const Go1TerrainConfig* cfg, const Go1TerrainBuffers* buf) { TerrainArgs A; A.c = *cfg; A.b = *buf; return A; }
-}  // namespace
 
 extern "C" int go1eval_terrain_clear(const Go1TerrainConfig* cfg, const Go1TerrainBuffers* buf, void* stream) {
   if (int rc = check(cfg, buf)) return rc;
-  const TerrainArgs A = args_of(cfg, buf);
-  hipLaunchKernelGGL(terrain_clear_kernel, env_grid(cfg->num_envs), dim3(ACC_THREADS), 0, (hipStream_t)stream, A);
-  return hipGetLastError() == hipSuccess ? 0 : -20;
+  return launch(terrain_clear_kernel, env_grid(cfg->num_envs), ACC_THREADS, stream, cfg, buf);
 }
 
 extern "C" int go1eval_terrain_accumulate(const Go1TerrainConfig* cfg, const Go1TerrainBuffers* buf, void* stream) {
@@ -1035,38 +987,20 @@ extern "C" int go1eval_terrain_accumulate(const Go1TerrainConfig* cfg, const Go1
       !buf->foot_indices || !buf->env_origins || !buf->reset_buf || !buf->time_out_buf || !buf->episode_length_buf) return -3;
   if (buf->height_samples && (cfg->hf_rows < 2 || cfg->hf_cols < 2)) return -12;
   if (!(cfg->hf_hscale > 0.0f && cfg->tile_length > 0.0f && cfg->tile_width > 0.0f && cfg->dt > 0.0f)) return -12;
-  const TerrainArgs A = args_of(cfg, buf);
-  hipLaunchKernelGGL(terrain_accumulate_kernel, env_grid(cfg->num_envs), dim3(ACC_THREADS), 0, (hipStream_t)stream, A);
-  return hipGetLastError() == hipSuccess ? 0 : -20;
+  return launch(terrain_accumulate_kernel, env_grid(cfg->num_envs), ACC_THREADS, stream, cfg, buf);
 }
 
 extern "C" int go1eval_terrain_reduce(const Go1TerrainConfig* cfg, const Go1TerrainBuffers* buf, void* stream) {
   if (int rc = check(cfg, buf)) return rc;
-  if (cfg->num_groups <= 0 || !buf->group || !buf->results) return -5;
+  if (!has_table(cfg, buf)) return -5;
   if (!(cfg->dt > 0.0f)) return -12;
-  const TerrainArgs A = args_of(cfg, buf);
-  hipLaunchKernelGGL(terrain_reduce_kernel, dim3((unsigned)(cfg->num_groups * (NTM + NTO + 1))), dim3(RT), 0, (hipStream_t)stream, A);
-  return hipGetLastError() == hipSuccess ? 0 : -20;
+  return launch(terrain_reduce_kernel, table_grid(cfg->num_groups, NTM + NTO + 1), RT, stream, cfg, buf);
 }
-
-namespace {
-int check(const Go1JointConfig* cfg, const Go1JointBuffers* buf) {
-  if (!cfg || !buf || cfg->num_envs <= 0) return -1;
-  if (!buf->count || !buf->sum || !buf->sumsq || !buf->min || !buf->max || !buf->nonfinite || !buf->prev_dof_vel || !buf->steps ||
-      !buf->resets || !buf->hist) return -2;
-  return 0;
-}
-JointArgs args_of(const Go1JointConfig* cfg, const Go1JointBuffers* buf) { JointArgs A; A.c = *cfg; A.b = *buf; return A; }
-dim3 joint_grid(int n) { return dim3((unsigned)(DOF * ((n + ACC_THREADS - 1) / ACC_THREADS))); }
-bool positive(float x) { return x > 0.0f && x <= 3.402823466e38f; }            // finite and positive (a NaN fails both)
-}  // namespace
 
 extern "C" int go1eval_joint_clear(const Go1JointConfig* cfg, const Go1JointBuffers* buf, void* stream) {
   if (int rc = check(cfg, buf)) return rc;
   if (!buf->dof_vel) return -3;
-  const JointArgs A = args_of(cfg, buf);
-  hipLaunchKernelGGL(joint_clear_kernel, joint_grid(cfg->num_envs), dim3(ACC_THREADS), 0, (hipStream_t)stream, A);
-  return hipGetLastError() == hipSuccess ? 0 : -20;
+  return launch(joint_clear_kernel, joint_grid(cfg->num_envs), ACC_THREADS, stream, cfg, buf);
 }
 
 extern "C" int go1eval_joint_accumulate(const Go1JointConfig* cfg, const Go1JointBuffers* buf, void* stream) {
@@ -1076,17 +1010,13 @@ extern "C" int go1eval_joint_accumulate(const Go1JointConfig* cfg, const Go1Join
   for (int j = 0; j < DOF; j++) {
     if (!(positive(cfg->torque_limit[j]) && positive(cfg->vel_limit[j]) && cfg->pos_lower[j] <= cfg->pos_upper[j])) return -12;
   }
-  const JointArgs A = args_of(cfg, buf);
-  hipLaunchKernelGGL(joint_accumulate_kernel, joint_grid(cfg->num_envs), dim3(ACC_THREADS), 0, (hipStream_t)stream, A);
-  return hipGetLastError() == hipSuccess ? 0 : -20;
+  return launch(joint_accumulate_kernel, joint_grid(cfg->num_envs), ACC_THREADS, stream, cfg, buf);
 }
 
 extern "C" int go1eval_joint_reduce(const Go1JointConfig* cfg, const Go1JointBuffers* buf, void* stream) {
   if (int rc = check(cfg, buf)) return rc;
-  if (cfg->num_groups <= 0 || !buf->group || !buf->results || !buf->hist_results) return -5;
-  const JointArgs A = args_of(cfg, buf);
-  hipLaunchKernelGGL(joint_reduce_kernel, dim3((unsigned)(cfg->num_groups * (DOF * NJ + 1 + DOF))), dim3(RT), 0, (hipStream_t)stream, A);
-  return hipGetLastError() == hipSuccess ? 0 : -20;
+  if (!has_table(cfg, buf) || !buf->hist_results) return -5;
+  return launch(joint_reduce_kernel, table_grid(cfg->num_groups, DOF * NJ + 1 + DOF), RT, stream, cfg, buf);
 }
 
 #ifndef GO1_SOURCE_HASH

@@ -594,40 +594,49 @@ class LeggedRobot(BaseTask):
         if self.buffers.device.type != "cuda":
             raise NotImplementedError(f"{what}(): the metrics are a HIP library; this simulator's buffers are not on a GPU")
 
+    def _family(self, what, attr, make):
+        """for the hook `what`: the family object kept under `attr`, made by make(go1eval_host) on first use (the library is not
+        imported before that)"""
+        self._need_gpu_metrics(what)
+        if getattr(self, attr) is None:
+            import go1eval_host
+            setattr(self, attr, make(go1eval_host))
+        return getattr(self, attr)
+
+    def _started(self, what, attr, start):
+        """for the hook `what`: the family object kept under `attr`, which the hook `start` makes"""
+        self._need_gpu_metrics(what)
+        if getattr(self, attr) is None:
+            raise RuntimeError(f"{what}(): {start}() was never called")
+        return getattr(self, attr)
+
+    def _disarm(self, what, *attrs):
+        """for the hook `what`: stop the family objects kept under `attrs` that exist; what they measured stays readable"""
+        self._need_gpu_metrics(what)
+        for attr in attrs:
+            if getattr(self, attr) is not None:
+                getattr(self, attr).disarm()
+
     def start_metrics(self, groups, warmup_steps=0, behaviour=False):
         """begin a measurement: `groups` = one int per environment (the row of the result table it counts towards, -1 = not
         evaluated); steps with episode_length_buf <= warmup_steps count towards no metric.  behaviour=True also arms the
         behaviour table (gait, body height, attitude, foot placement and stride tracking): one more launch per step"""
-        self._need_gpu_metrics("start_metrics")
-        if self._metrics is None:
-            import go1eval_host
-            self._metrics = go1eval_host.Go1Eval(self.sim_config, self.buffers)
-        self._metrics.arm(groups, warmup_steps)
+        self._family("start_metrics", "_metrics", lambda G: G.Go1Eval(self.sim_config, self.buffers)).arm(groups, warmup_steps)
         if behaviour:
-            if self._behaviour is None:
-                import go1eval_host
-                self._behaviour = go1eval_host.Go1Behaviour(self.sim_config, self.buffers, self.dt)
-            self._behaviour.arm(groups, warmup_steps)
+            self._family("start_metrics", "_behaviour", lambda G: G.Go1Behaviour(self.sim_config, self.buffers, self.dt)).arm(groups, warmup_steps)
         elif self._behaviour is not None:
             self._behaviour.disarm()
             self._behaviour.table = None          # a measurement without the behaviour table reads none
 
     def stop_metrics(self):
         """stop folding steps; what was measured stays readable"""
-        self._need_gpu_metrics("stop_metrics")
-        if self._metrics is not None:
-            self._metrics.disarm()
-        if self._behaviour is not None:
-            self._behaviour.disarm()
+        self._disarm("stop_metrics", "_metrics", "_behaviour")
 
     def read_metrics(self):
         """{metric name: (groups, 6) array of count, mean, std, min, max, nonfinite; "groups": (groups, 5) array of envs, steps,
         episodes_terminated, episodes_timed_out, fall_rate}: one reduction launch and one device-to-host copy.  After
         start_metrics(behaviour=True) also "behaviour": {behaviour metric name: (groups, 6) array}, by one more of each"""
-        self._need_gpu_metrics("read_metrics")
-        if self._metrics is None:
-            raise RuntimeError("read_metrics(): start_metrics() was never called")
-        res = self._metrics.results()
+        res = self._started("read_metrics", "_metrics", "start_metrics").results()
         if self._behaviour is not None and self._behaviour.table is not None:
             res["behaviour"] = self._behaviour.results()
         return res
@@ -638,32 +647,22 @@ class LeggedRobot(BaseTask):
     def start_trace(self, env_ids=None, capacity=None):
         """begin a trace of the environments `env_ids` (None: all) with room for `capacity` steps (default: an episode,
         max_episode_length + 2); steps beyond the capacity are not recorded"""
-        self._need_gpu_metrics("start_trace")
-        if self._trace is None:
-            import go1eval_host
-            self._trace = go1eval_host.Go1Trace(self.sim_config, self.buffers)
-        self._trace.arm(env_ids, int(self.max_episode_length) + 2 if capacity is None else capacity)
+        trace = self._family("start_trace", "_trace", lambda G: G.Go1Trace(self.sim_config, self.buffers))
+        trace.arm(env_ids, int(self.max_episode_length) + 2 if capacity is None else capacity)
 
     def stop_trace(self):
         """stop recording; what was recorded stays readable"""
-        self._need_gpu_metrics("stop_trace")
-        if self._trace is not None:
-            self._trace.disarm()
+        self._disarm("stop_trace", "_trace")
 
     def read_trace(self):
         """{channel name: (rows, K) float32 array, "env_ids", "rows", "truncated"}: one device-to-host copy"""
-        self._need_gpu_metrics("read_trace")
-        if self._trace is None:
-            raise RuntimeError("read_trace(): start_trace() was never called")
-        return self._trace.read()
+        return self._started("read_trace", "_trace", "start_trace").read()
 
     def trace_response(self, signals, switch_row, pre, smooth, band, hold, tail, groups, dt=None):
         """the step response of the recorded trace around the command switch at row `switch_row` (go1eval_host.Go1Trace.response;
         dt defaults to the policy step): two launches and one device-to-host copy"""
-        self._need_gpu_metrics("trace_response")
-        if self._trace is None:
-            raise RuntimeError("trace_response(): start_trace() was never called")
-        return self._trace.response(signals, switch_row, pre, smooth, band, hold, tail, self.dt if dt is None else dt, groups)
+        trace = self._started("trace_response", "_trace", "start_trace")
+        return trace.response(signals, switch_row, pre, smooth, band, hold, tail, self.dt if dt is None else dt, groups)
 
     # ---- the push and the recovery from it (include/go1eval.h, fourth kernel family).  The reference's _push_robots draws a random
     # planar velocity at a fixed interval and REPLACES the base velocity; this one ADDS a chosen velocity step to chosen environments.
@@ -671,20 +670,15 @@ class LeggedRobot(BaseTask):
         """add a velocity step to the base of the environments `env_ids` (None: all, in order) now, between two step() calls:
         push (K, 4) array or tensor of forward, left (the robot's heading frame), up (m/s) and yaw rate (rad/s) steps.  One launch
         on the simulator's stream; the table is checked on the host first (finite, no id twice, ids in range)."""
-        self._need_gpu_metrics("push_robots")
-        if self._push is None:
-            import go1eval_host
-            self._push = go1eval_host.Go1Push(self.sim_config, self.buffers)
-        self._push.load(push, env_ids)
-        self._push.launch()
+        pusher = self._family("push_robots", "_push", lambda G: G.Go1Push(self.sim_config, self.buffers))
+        pusher.load(push, env_ids)
+        pusher.launch()
 
     def trace_recovery(self, push_row, pre, smooth, band, hold, groups, dt=None):
         """the recovery of the recorded trace from the push before row `push_row` (go1eval_host.Go1Trace.recovery; dt defaults to
         the policy step): two launches and one device-to-host copy"""
-        self._need_gpu_metrics("trace_recovery")
-        if self._trace is None:
-            raise RuntimeError("trace_recovery(): start_trace() was never called")
-        return self._trace.recovery(push_row, pre, smooth, band, hold, self.dt if dt is None else dt, groups)
+        trace = self._started("trace_recovery", "_trace", "start_trace")
+        return trace.recovery(push_row, pre, smooth, band, hold, self.dt if dt is None else dt, groups)
 
     # ---- terrain traversal (include/go1eval.h, fifth kernel family): does a robot leave the tile it was placed on, fall or time out
     # first, and how high are its base and feet above the ground they are over.  One more launch per step while it is armed, after the
@@ -721,28 +715,20 @@ class LeggedRobot(BaseTask):
         not evaluated).  Every environment is measured from now for its first episode on its home tile (env_origins +- half a
         tile: terrain_length x terrain_width, or env_spacing in both directions on the plane); steps with episode_length_buf <=
         warmup_steps fold no metric"""
-        self._need_gpu_metrics("start_terrain_metrics")
-        if self._traversal is None:
-            import go1eval_host
-            ter = self.cfg.terrain
-            tile = (ter.terrain_length, ter.terrain_width) if ter.mesh_type in ("heightfield", "trimesh") else (self.cfg.env.env_spacing,) * 2
-            self._traversal = go1eval_host.Go1Terrain(self.sim_config, self.buffers, self.dt, *tile)
-        self._traversal.arm(groups, warmup_steps)
+        ter = self.cfg.terrain
+        tile = (ter.terrain_length, ter.terrain_width) if ter.mesh_type in ("heightfield", "trimesh") else (self.cfg.env.env_spacing,) * 2
+        traversal = self._family("start_terrain_metrics", "_traversal", lambda G: G.Go1Terrain(self.sim_config, self.buffers, self.dt, *tile))
+        traversal.arm(groups, warmup_steps)
 
     def stop_terrain_metrics(self):
         """stop folding steps; what was measured stays readable"""
-        self._need_gpu_metrics("stop_terrain_metrics")
-        if self._traversal is not None:
-            self._traversal.disarm()
+        self._disarm("stop_terrain_metrics", "_traversal")
 
     def read_terrain_metrics(self):
         """go1eval_host.Go1Terrain.read(): {"metrics": {name: (groups, 6)}, "outcomes": {name: (groups, 6)}, "groups": (groups, 6) array
         of envs, running, traversed, fell, timed_out, success_rate, "status", "steps", "end_step", "max_dist": per environment}: one
         reduction launch and the device-to-host copies"""
-        self._need_gpu_metrics("read_terrain_metrics")
-        if self._traversal is None:
-            raise RuntimeError("read_terrain_metrics(): start_terrain_metrics() was never called")
-        return self._traversal.read()
+        return self._started("read_terrain_metrics", "_traversal", "start_terrain_metrics").read()
 
     # ---- per-joint actuator usage (include/go1eval.h, sixth kernel family): ten values per joint and step and a torque-speed histogram
     # per joint.  One more launch per step while it is armed, after the terrain family's; independent of the other measurements.
@@ -751,29 +737,21 @@ class LeggedRobot(BaseTask):
         evaluated); steps with episode_length_buf <= warmup_steps fold nothing.  Saturation is tested against
         rewards.soft_torque_limit x the simulator's torque limit and rewards.soft_dof_vel_limit x the URDF's speed limit (a factor
         the configuration does not carry is 1)"""
-        self._need_gpu_metrics("start_joint_metrics")
-        if self._joints is None:
-            import go1eval_host
-            rewards = self.cfg.rewards
-            self._joints = go1eval_host.Go1Joints(self.sim_config, self.buffers, self.dt, H._DOF_VELOCITY,
-                                                  soft_torque_limit=float(getattr(rewards, "soft_torque_limit", 1.0)),
-                                                  soft_vel_limit=float(getattr(rewards, "soft_dof_vel_limit", 1.0)))
-        self._joints.arm(groups, warmup_steps)
+        rewards = self.cfg.rewards
+        joints = self._family("start_joint_metrics", "_joints", lambda G: G.Go1Joints(
+            self.sim_config, self.buffers, self.dt, H._DOF_VELOCITY, soft_torque_limit=float(getattr(rewards, "soft_torque_limit", 1.0)),
+            soft_vel_limit=float(getattr(rewards, "soft_dof_vel_limit", 1.0))))
+        joints.arm(groups, warmup_steps)
 
     def stop_joint_metrics(self):
         """stop folding steps; what was measured stays readable"""
-        self._need_gpu_metrics("stop_joint_metrics")
-        if self._joints is not None:
-            self._joints.disarm()
+        self._disarm("stop_joint_metrics", "_joints")
 
     def read_joint_metrics(self):
         """go1eval_host.Go1Joints.read(): {"metrics": {name: (groups, 12, 6)}, "groups": (groups, 3) array of envs, steps, resets, "hist":
         (groups, 12, 8, 8) torque-bin x speed-bin counts, "tau_edges", "vel_edges": (12, 9), and the per-environment "steps", "resets",
         "prev_dof_vel", "env_hist"}: one reduction launch and the device-to-host copies"""
-        self._need_gpu_metrics("read_joint_metrics")
-        if self._joints is None:
-            raise RuntimeError("read_joint_metrics(): start_joint_metrics() was never called")
-        return self._joints.read()
+        return self._started("read_joint_metrics", "_joints", "start_joint_metrics").read()
 
     def render(self, mode="rgb_array"):
         """reference :1612-1620: env 0 from its recording camera, now: (240, 360, 4) uint8 RGBA"""

@@ -11,6 +11,12 @@ terrain tile it was placed on, falls or times out first, and its height, foot cl
 it is over, from the simulator's own height field.  `Go1Joints` is the sixth: ten values per joint and step (torque, speed,
 acceleration, driving and braking power, soft-limit excess, saturation at the torque clip and at the URDF's speed limit) and a
 torque-speed histogram per joint.
+
+What the families share is written once: `load_library` declares the entry points from one table (`_ENTRY_POINTS`); `_Host` holds
+the library, the simulator's buffers and how a launch is made and checked; `_Table` is the accumulating family (accumulators,
+per-environment state, groups and result table, arm / accumulate / disarm / reduce), which `Go1Eval`, `Go1Behaviour`, `Go1Terrain`
+and `Go1Joints` describe with a few class attributes; `_groups` and `_env_ids` are the two host-side validations; and
+`Go1Trace._analysis` is the shared back half of the response and the recovery.
 """
 import ctypes
 import os
@@ -180,6 +186,17 @@ EXPORTED_SYMBOLS = ["go1eval_clear", "go1eval_accumulate", "go1eval_reduce", "go
                     "go1eval_terrain_clear", "go1eval_terrain_accumulate", "go1eval_terrain_reduce",
                     "go1eval_joint_clear", "go1eval_joint_accumulate", "go1eval_joint_reduce"]
 
+# (entry points, config, buffers): each is f(const config*, const buffers*, void* stream) -> int; go1eval_trace_record alone takes
+# the row (int32) in front of the stream
+_ENTRY_POINTS = [(("go1eval_clear", "go1eval_accumulate", "go1eval_reduce"), Go1EvalConfig, Go1EvalBuffers),
+                 (("go1eval_behaviour_clear", "go1eval_behaviour_accumulate", "go1eval_behaviour_reduce"), Go1BehaviourConfig, Go1BehaviourBuffers),
+                 (("go1eval_trace_record",), Go1TraceConfig, Go1TraceBuffers),
+                 (("go1eval_response", "go1eval_response_reduce"), Go1ResponseConfig, Go1ResponseBuffers),
+                 (("go1eval_push",), Go1PushConfig, Go1PushBuffers),
+                 (("go1eval_recovery", "go1eval_recovery_reduce"), Go1RecoveryConfig, Go1RecoveryBuffers),
+                 (("go1eval_terrain_clear", "go1eval_terrain_accumulate", "go1eval_terrain_reduce"), Go1TerrainConfig, Go1TerrainBuffers),
+                 (("go1eval_joint_clear", "go1eval_joint_accumulate", "go1eval_joint_reduce"), Go1JointConfig, Go1JointBuffers)]
+
 _lib = None
 
 
@@ -198,70 +215,59 @@ def load_library(path=None):
             f"{p} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
             f"(hipcc --offload-arch=gfx950). Device-side evaluation metrics have no CPU fallback.")
     lib = ctypes.CDLL(p)
-    cfg_p, buf_p = ctypes.POINTER(Go1EvalConfig), ctypes.POINTER(Go1EvalBuffers)
-    for fn in ("go1eval_clear", "go1eval_accumulate", "go1eval_reduce"):
-        getattr(lib, fn).argtypes = [cfg_p, buf_p, ctypes.c_void_p]
-        getattr(lib, fn).restype = ctypes.c_int
-    cfg_p, buf_p = ctypes.POINTER(Go1BehaviourConfig), ctypes.POINTER(Go1BehaviourBuffers)
-    for fn in ("go1eval_behaviour_clear", "go1eval_behaviour_accumulate", "go1eval_behaviour_reduce"):
-        getattr(lib, fn).argtypes = [cfg_p, buf_p, ctypes.c_void_p]
-        getattr(lib, fn).restype = ctypes.c_int
-    lib.go1eval_trace_record.argtypes = [ctypes.POINTER(Go1TraceConfig), ctypes.POINTER(Go1TraceBuffers), ctypes.c_int32, ctypes.c_void_p]
-    lib.go1eval_trace_record.restype = ctypes.c_int
-    for fn in ("go1eval_response", "go1eval_response_reduce"):
-        getattr(lib, fn).argtypes = [ctypes.POINTER(Go1ResponseConfig), ctypes.POINTER(Go1ResponseBuffers), ctypes.c_void_p]
-        getattr(lib, fn).restype = ctypes.c_int
-    lib.go1eval_push.argtypes = [ctypes.POINTER(Go1PushConfig), ctypes.POINTER(Go1PushBuffers), ctypes.c_void_p]
-    lib.go1eval_push.restype = ctypes.c_int
-    for fn in ("go1eval_recovery", "go1eval_recovery_reduce"):
-        getattr(lib, fn).argtypes = [ctypes.POINTER(Go1RecoveryConfig), ctypes.POINTER(Go1RecoveryBuffers), ctypes.c_void_p]
-        getattr(lib, fn).restype = ctypes.c_int
-    for fn in ("go1eval_terrain_clear", "go1eval_terrain_accumulate", "go1eval_terrain_reduce"):
-        getattr(lib, fn).argtypes = [ctypes.POINTER(Go1TerrainConfig), ctypes.POINTER(Go1TerrainBuffers), ctypes.c_void_p]
-        getattr(lib, fn).restype = ctypes.c_int
-    for fn in ("go1eval_joint_clear", "go1eval_joint_accumulate", "go1eval_joint_reduce"):
-        getattr(lib, fn).argtypes = [ctypes.POINTER(Go1JointConfig), ctypes.POINTER(Go1JointBuffers), ctypes.c_void_p]
-        getattr(lib, fn).restype = ctypes.c_int
+    for symbols, config, buffers in _ENTRY_POINTS:
+        for fn in symbols:
+            row = [ctypes.c_int32] if fn == "go1eval_trace_record" else []
+            getattr(lib, fn).argtypes = [ctypes.POINTER(config), ctypes.POINTER(buffers)] + row + [ctypes.c_void_p]
+            getattr(lib, fn).restype = ctypes.c_int
     lib.go1eval_version.restype = ctypes.c_char_p
     if path is None:
         _lib = lib
     return lib
 
 
-_ACC_DTYPES = {"count": torch.int32, "sum": torch.float64, "sumsq": torch.float64, "min": torch.float32, "max": torch.float32,
-               "nonfinite": torch.int32}          # (uint32 on the device; torch reads the same bits as int32)
+def _groups(groups, count, member="environment"):
+    """(group ids as a flat int32 tensor, G = the largest id + 1) of `groups`: one int per member, -1 = not evaluated"""
+    g = torch.as_tensor(groups).to(torch.int32).reshape(-1)
+    assert g.numel() == count, (g.numel(), count)
+    G = int(g.max()) + 1                                       # (on the host, before the step loop)
+    assert G >= 1, f"no {member} carries a group id >= 0"
+    return g, G
 
 
-class Go1Eval:
-    """Metrics of one simulator instance.  S: its Go1SimConfig, buffers: its SimBuffers (device tensors)."""
+def _env_ids(env_ids, N, word, rows=None):
+    """`env_ids` as a flat int64 array on the host, refused unless there are `rows` of them (None: any number but none), all in
+    [0, N) and none named twice; `word` names the caller in the message"""
+    ids = np.asarray(torch.as_tensor(env_ids).cpu(), dtype=np.int64).reshape(-1)                # (on the host, before the step loop)
+    if rows is not None and ids.size != rows:
+        raise ValueError(f"{word}: {ids.size} environment ids for {rows} rows")
+    if ids.size == 0 or ids.min() < 0 or ids.max() >= N:
+        raise ValueError(f"{word}: environment ids have to lie in [0, {N})")
+    if np.unique(ids).size != ids.size:
+        raise ValueError(f"{word}: an environment is named twice")
+    return ids
 
-    def __init__(self, S, buffers, lib=None):
+
+class _Host:
+    """What every family's host object holds: the library, the simulator's buffers, and how a launch is made and checked."""
+    measure_heights = False
+
+    def __init__(self, buffers, lib=None):
         self.lib = lib if lib is not None else load_library()
         self.buffers = buffers
         self.device = buffers.device
-        N = self.num_envs = int(S.num_envs)
-        c = self.cfg = Go1EvalConfig()
-        c.num_envs, c.default_body_mass = N, DEFAULT_BODY_MASS
-        self.measure_heights = bool(S.measure_heights)
-        c.num_height_points = int(buffers.measured_heights.shape[0]) if self.measure_heights else 0
-        self.acc = {n: torch.zeros(NUM_METRICS, N, dtype=dt, device=self.device) for n, dt in _ACC_DTYPES.items()}
-        self.per_env = {n: torch.zeros(N, dtype=torch.int32, device=self.device) for n in _PER_ENV}
-        self.group = torch.full((N,), -1, dtype=torch.int32, device=self.device)
-        self.table = None
-        self.armed = False
-        self.buf = Go1EvalBuffers()
-        self._refresh()
 
-    def _refresh(self):
-        b, B = self.buf, self.buffers
-        for n in _INPUTS:
-            setattr(b, n, getattr(B, n).data_ptr())
-        if not self.measure_heights:
-            b.measured_heights = None
-        for n, t in list(self.acc.items()) + list(self.per_env.items()):
-            setattr(b, n, t.data_ptr())
-        b.group = self.group.data_ptr()
-        b.results = self.table.data_ptr() if self.table is not None else None
+    def _heights(self, S):
+        """base heights are taken above measured_heights if the simulator measures them, else above z = 0"""
+        self.measure_heights = bool(S.measure_heights)
+        self.cfg.num_height_points = int(self.buffers.measured_heights.shape[0]) if self.measure_heights else 0
+
+    def _bind(self, buf, names):
+        """the simulator's tensors `names` into buf; NULL for one it does not have, and for heights that are not measured"""
+        for n in names:
+            t = getattr(self.buffers, n)
+            bound = t is not None and (n != "measured_heights" or self.measure_heights)
+            setattr(buf, n, t.data_ptr() if bound else None)
 
     def _stream(self):
         return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -270,32 +276,88 @@ class Go1Eval:
         if rc != 0:
             raise RuntimeError(f"{what} failed: {rc}")
 
+    def _launch(self, name, cfg, buf, *row):
+        self._check(getattr(self.lib, name)(ctypes.byref(cfg), ctypes.byref(buf), *row, self._stream()), name)
+
+
+_ACC_DTYPES = {"count": torch.int32, "sum": torch.float64, "sumsq": torch.float64, "min": torch.float32, "max": torch.float32,
+               "nonfinite": torch.int32}          # (uint32 on the device; torch reads the same bits as int32)
+
+
+class _Table(_Host):
+    """An accumulating family of one simulator instance: it owns the accumulators ([ROWS][N]), its per-environment state, the
+    group ids and the result table ([G][TABLE_ROWS][NUM_FIELDS]), and launches PREFIX_clear / _accumulate / _reduce.  A family
+    names these, sets what else its config holds, and reads its table."""
+    PREFIX = CONFIG = BUFFERS = None
+    INPUTS, ROWS, TABLE_ROWS = (), 0, 0
+    STATE_ATTR, STATE = "state", {}               # the attribute the state tensors live under; {name: (dtype, dimensions in front of [N])}
+
+    def __init__(self, S, buffers, lib=None):
+        super().__init__(buffers, lib)
+        N = self.num_envs = int(S.num_envs)
+        self.cfg = self.CONFIG()
+        self.cfg.num_envs = N
+        self.acc = {n: torch.zeros(self.ROWS, N, dtype=dt, device=self.device) for n, dt in _ACC_DTYPES.items()}
+        setattr(self, self.STATE_ATTR, {n: torch.zeros(*lead, N, dtype=dt, device=self.device) for n, (dt, lead) in self.STATE.items()})
+        self.group = torch.full((N,), -1, dtype=torch.int32, device=self.device)
+        self.table = None
+        self.armed = False
+        self.buf = self.BUFFERS()
+
+    def _refresh(self):
+        b = self.buf
+        self._bind(b, self.INPUTS)
+        for n, t in list(self.acc.items()) + list(getattr(self, self.STATE_ATTR).items()):
+            setattr(b, n, t.data_ptr())
+        b.group = self.group.data_ptr()
+        b.results = self.table.data_ptr() if self.table is not None else None
+
+    def _call(self, name):
+        self._launch(name, self.cfg, self.buf)
+
+    def _size_tables(self, G):
+        self.table = torch.zeros(G, self.TABLE_ROWS, NUM_FIELDS, dtype=torch.float64, device=self.device)
+
+    def clear(self):
+        """empty accumulators and the family's state as at the start of a measurement (one launch, no sync)"""
+        self._call(self.PREFIX + "_clear")
+
     def arm(self, groups, warmup_steps=0):
-        """start a measurement: `groups` = int group id per environment (-1: not evaluated); empties the accumulators"""
-        g = torch.as_tensor(groups).to(torch.int32).reshape(-1)
-        assert g.numel() == self.num_envs, (g.numel(), self.num_envs)
-        G = int(g.max()) + 1                                   # (on the host, before the step loop)
-        assert G >= 1, "no environment carries a group id >= 0"
+        """start a measurement: `groups` = int group id per environment (-1: not evaluated); sizes the table and clears"""
+        g, G = _groups(groups, self.num_envs)
         self.group.copy_(g)
         self.cfg.num_groups, self.cfg.warmup_steps = G, int(warmup_steps)
-        self.table = torch.zeros(G, NUM_METRICS + 1, NUM_FIELDS, dtype=torch.float64, device=self.device)
+        self._size_tables(G)
         self._refresh()
-        self._check(self.lib.go1eval_clear(ctypes.byref(self.cfg), ctypes.byref(self.buf), self._stream()), "go1eval_clear")
+        self.clear()
         self.armed = True
 
     def accumulate(self):
-        """after a step: fold it into the accumulators (one launch, no sync)"""
-        self._check(self.lib.go1eval_accumulate(ctypes.byref(self.cfg), ctypes.byref(self.buf), self._stream()), "go1eval_accumulate")
+        """after a step: fold it into the accumulators and advance the family's state (one launch, no sync)"""
+        self._call(self.PREFIX + "_accumulate")
 
     def disarm(self):
-        """stop folding steps (the accumulators keep what they hold for `results()`)"""
+        """stop folding steps (the accumulators keep what they hold for the next read)"""
         self.armed = False
 
     def reduce(self):
-        """the result table [G][NUM_METRICS + 1][NUM_FIELDS] as a device tensor (one launch, no sync)"""
+        """the result table [G][TABLE_ROWS][NUM_FIELDS] as a device tensor (one launch, no sync)"""
         assert self.table is not None, "arm() first"
-        self._check(self.lib.go1eval_reduce(ctypes.byref(self.cfg), ctypes.byref(self.buf), self._stream()), "go1eval_reduce")
+        self._call(self.PREFIX + "_reduce")
         return self.table
+
+
+class Go1Eval(_Table):
+    """Metrics of one simulator instance.  S: its Go1SimConfig, buffers: its SimBuffers (device tensors)."""
+    PREFIX, CONFIG, BUFFERS, INPUTS = "go1eval", Go1EvalConfig, Go1EvalBuffers, _INPUTS
+    ROWS, TABLE_ROWS = NUM_METRICS, NUM_METRICS + 1
+    STATE_ATTR, STATE = "per_env", {n: (torch.int32, ()) for n in _PER_ENV}
+
+    def __init__(self, S, buffers, lib=None):
+        super().__init__(S, buffers, lib)
+        self.cfg.default_body_mass = DEFAULT_BODY_MASS
+        self._heights(S)
+        self._refresh()
 
     def results(self):
         """{metric name: (G, 6) array with the columns FIELD_NAMES, "groups": (G, 5) array with the columns GROUP_FIELD_NAMES}:
@@ -309,71 +371,21 @@ def table_to_dict(table):
     return out
 
 
-_STRIDE_DTYPES = {"prev_contact": torch.uint8, "stride_steps": torch.int32, "stance_steps": torch.int32, "swing_peak": torch.float32}
-
-
-class Go1Behaviour:
-    """The behaviour table of one simulator instance, beside `Go1Eval`: it owns its accumulators and the per-foot stride state.
-    S: the simulator's Go1SimConfig, buffers: its SimBuffers (device tensors), dt: the policy step in seconds."""
+class Go1Behaviour(_Table):
+    """The behaviour table of one simulator instance, beside `Go1Eval`: it owns its accumulators and the per-foot stride state,
+    which arm() forgets.  S: the simulator's Go1SimConfig, buffers: its SimBuffers (device tensors), dt: the policy step in seconds."""
+    PREFIX, CONFIG, BUFFERS, INPUTS = "go1eval_behaviour", Go1BehaviourConfig, Go1BehaviourBuffers, _BEHAVIOUR_INPUTS
+    ROWS, TABLE_ROWS = NUM_BEHAVIOUR, NUM_BEHAVIOUR
+    STATE_ATTR = "stride"
+    STATE = {"prev_contact": (torch.uint8, (4,)), "stride_steps": (torch.int32, (4,)), "stance_steps": (torch.int32, (4,)),
+             "swing_peak": (torch.float32, (4,))}
 
     def __init__(self, S, buffers, dt, lib=None):
-        self.lib = lib if lib is not None else load_library()
-        self.buffers = buffers
-        self.device = buffers.device
-        N = self.num_envs = int(S.num_envs)
-        c = self.cfg = Go1BehaviourConfig()
-        c.num_envs, c.num_commands, c.dt, c.base_height_target = N, int(S.num_commands), float(dt), float(S.base_height_target)
-        self.measure_heights = bool(S.measure_heights)
-        c.num_height_points = int(buffers.measured_heights.shape[0]) if self.measure_heights else 0
-        self.acc = {n: torch.zeros(NUM_BEHAVIOUR, N, dtype=dt_, device=self.device) for n, dt_ in _ACC_DTYPES.items()}
-        self.stride = {n: torch.zeros(4, N, dtype=dt_, device=self.device) for n, dt_ in _STRIDE_DTYPES.items()}
-        self.group = torch.full((N,), -1, dtype=torch.int32, device=self.device)
-        self.table = None
-        self.armed = False
-        self.buf = Go1BehaviourBuffers()
+        super().__init__(S, buffers, lib)
+        c = self.cfg
+        c.num_commands, c.dt, c.base_height_target = int(S.num_commands), float(dt), float(S.base_height_target)
+        self._heights(S)
         self._refresh()
-
-    def _refresh(self):
-        b, B = self.buf, self.buffers
-        for n in _BEHAVIOUR_INPUTS:
-            setattr(b, n, getattr(B, n).data_ptr())
-        if not self.measure_heights:
-            b.measured_heights = None
-        for n, t in list(self.acc.items()) + list(self.stride.items()):
-            setattr(b, n, t.data_ptr())
-        b.group = self.group.data_ptr()
-        b.results = self.table.data_ptr() if self.table is not None else None
-
-    _stream, _check = Go1Eval._stream, Go1Eval._check
-
-    def _call(self, name):
-        self._check(getattr(self.lib, name)(ctypes.byref(self.cfg), ctypes.byref(self.buf), self._stream()), name)
-
-    def arm(self, groups, warmup_steps=0):
-        """start a measurement (as Go1Eval.arm): empties the accumulators and forgets every stride"""
-        g = torch.as_tensor(groups).to(torch.int32).reshape(-1)
-        assert g.numel() == self.num_envs, (g.numel(), self.num_envs)
-        G = int(g.max()) + 1
-        assert G >= 1, "no environment carries a group id >= 0"
-        self.group.copy_(g)
-        self.cfg.num_groups, self.cfg.warmup_steps = G, int(warmup_steps)
-        self.table = torch.zeros(G, NUM_BEHAVIOUR, NUM_FIELDS, dtype=torch.float64, device=self.device)
-        self._refresh()
-        self._call("go1eval_behaviour_clear")
-        self.armed = True
-
-    def accumulate(self):
-        """after a step: fold it and advance the stride state (one launch, no sync)"""
-        self._call("go1eval_behaviour_accumulate")
-
-    def disarm(self):
-        self.armed = False
-
-    def reduce(self):
-        """the result table [G][NUM_BEHAVIOUR][NUM_FIELDS] as a device tensor (one launch, no sync)"""
-        assert self.table is not None, "arm() first"
-        self._call("go1eval_behaviour_reduce")
-        return self.table
 
     def results(self):
         """{behaviour metric name: (G, 6) array with the columns FIELD_NAMES}: one launch and one device-to-host copy"""
@@ -394,24 +406,19 @@ def response_signals(cfg, signals):
     return names
 
 
-class Go1Trace:
+class Go1Trace(_Host):
     """The trace of one simulator instance: a ring of `capacity` rows x 24 channels x K traced environments on the device, one
     launch per recorded step, and the step-response analysis of what it holds.  S: the simulator's Go1SimConfig, buffers: its
     SimBuffers (device tensors).  Nothing is allocated before the first arm()."""
 
     def __init__(self, S, buffers, lib=None):
-        self.lib = lib if lib is not None else load_library()
-        self.buffers = buffers
-        self.device = buffers.device
+        super().__init__(buffers, lib)
         c = self.cfg = Go1TraceConfig()
         c.num_envs, c.base_height_target = int(S.num_envs), float(S.base_height_target)
-        self.measure_heights = bool(S.measure_heights)
-        c.num_height_points = int(buffers.measured_heights.shape[0]) if self.measure_heights else 0
+        self._heights(S)
         self.buf = Go1TraceBuffers()
         self.trace = self.ids = self.env_ids = None
         self.rows, self.truncated, self.armed = 0, False, False
-
-    _stream, _check = Go1Eval._stream, Go1Eval._check
 
     def arm(self, env_ids=None, capacity=1):
         """start a trace of the environments `env_ids` (None: all of them, in order) with room for `capacity` steps"""
@@ -419,12 +426,7 @@ class Go1Trace:
         if env_ids is None:
             self.env_ids, self.ids = np.arange(N, dtype=np.int32), None
         else:
-            ids = np.asarray(torch.as_tensor(env_ids).cpu(), dtype=np.int64).reshape(-1)            # (on the host, before the step loop)
-            if ids.size == 0 or ids.min() < 0 or ids.max() >= N:
-                raise ValueError(f"trace: environment ids have to lie in [0, {N})")
-            if np.unique(ids).size != ids.size:
-                raise ValueError("trace: an environment is named twice")
-            self.env_ids = ids.astype(np.int32)
+            self.env_ids = _env_ids(env_ids, N, "trace").astype(np.int32)
             self.ids = torch.from_numpy(self.env_ids).to(self.device)
         K, capacity = int(self.env_ids.size), int(capacity)
         if capacity < 1:
@@ -432,11 +434,8 @@ class Go1Trace:
         if self.trace is None or tuple(self.trace.shape) != (capacity, NUM_TRACE, K):
             self.trace = torch.zeros(capacity, NUM_TRACE, K, dtype=torch.float32, device=self.device)
         self.cfg.num_traced, self.cfg.capacity = K, capacity
-        b, B = self.buf, self.buffers
-        for n in _TRACE_INPUTS:
-            setattr(b, n, getattr(B, n).data_ptr())
-        if not self.measure_heights:
-            b.measured_heights = None
+        b = self.buf
+        self._bind(b, _TRACE_INPUTS)
         b.env_ids = self.ids.data_ptr() if self.ids is not None else None
         b.trace = self.trace.data_ptr()
         self.rows, self.truncated, self.armed = 0, False, True
@@ -446,7 +445,7 @@ class Go1Trace:
         if self.rows >= self.cfg.capacity:
             self.truncated = True
             return
-        self._check(self.lib.go1eval_trace_record(ctypes.byref(self.cfg), ctypes.byref(self.buf), self.rows, self._stream()), "go1eval_trace_record")
+        self._launch("go1eval_trace_record", self.cfg, self.buf, self.rows)
         self.rows += 1
 
     def disarm(self):
@@ -461,38 +460,41 @@ class Go1Trace:
         out.update(env_ids=self.env_ids.copy(), rows=self.rows, truncated=self.truncated)
         return out
 
+    def _analysis(self, c, buffers, symbols, V, groups):
+        """The back half of an analysis of the recorded rows: c = its config, filled but for num_traced, rows and num_groups,
+        buffers = its buffers type, symbols = (per-environment kernel's entry point, reduction's), V = values per traced
+        environment.  The table, the values and the status share one allocation (fp64 first: aligned), so two launches and one
+        device-to-host copy.  Returns (table (G, V + 1, 6) float64, values (V, K) float32, status (K,) int32) on the host."""
+        K = int(self.cfg.num_traced)
+        g, G = _groups(groups, K, "traced environment")
+        c.num_traced, c.rows, c.num_groups = K, self.rows, G
+        nbytes = [G * (V + 1) * NUM_FIELDS * 8, V * K * 4, K * 4]                     # results, values, status
+        out = torch.zeros(sum(nbytes), dtype=torch.uint8, device=self.device)
+        group = g.to(self.device)
+        b = buffers()
+        b.trace, b.group = self.trace.data_ptr(), group.data_ptr()
+        b.results, b.values, b.status = out.data_ptr(), out.data_ptr() + nbytes[0], out.data_ptr() + nbytes[0] + nbytes[1]
+        for name in symbols:
+            self._launch(name, c, b)
+        host = out.cpu().numpy()
+        return (host[:nbytes[0]].view(np.float64).reshape(G, V + 1, NUM_FIELDS), host[nbytes[0]:nbytes[0] + nbytes[1]].view(np.float32).reshape(V, K),
+                host[nbytes[0] + nbytes[1]:].view(np.int32).copy())
+
     def response(self, signals, switch_row, pre, smooth, band, hold, tail, dt, groups):
         """The step response of the recorded rows.  signals: {name: (y_channel, r_channel or None[, fixed_target, fixed_scale])};
         groups: one int per traced environment (-1: not evaluated).  Returns {signal: {metric: (G, 6) array with the columns
         FIELD_NAMES}}, "groups": (G, 4) array with the columns RESPONSE_GROUP_FIELDS, "values": {signal: {metric: (K,) float32}}
         and "status": (K,) int32.  Two launches and one device-to-host copy."""
         assert self.trace is not None, "arm() first"
-        K = int(self.cfg.num_traced)
         c = Go1ResponseConfig()
         names = response_signals(c, signals)
-        S = len(names)
-        g = torch.as_tensor(groups).to(torch.int32).reshape(-1)
-        assert g.numel() == K, (g.numel(), K)
-        G = int(g.max()) + 1
-        assert G >= 1, "no traced environment carries a group id >= 0"
-        c.num_traced, c.rows, c.switch_row, c.pre, c.smooth, c.hold, c.tail = K, self.rows, int(switch_row), int(pre), int(smooth), int(hold), int(tail)
-        c.band, c.dt, c.num_groups = float(band), float(dt), G
-        R = S * NUM_RESPONSE + 1
-        nbytes = [G * R * NUM_FIELDS * 8, S * NUM_RESPONSE * K * 4, K * 4]            # results (fp64 first: aligned), values, status
-        out = torch.zeros(sum(nbytes), dtype=torch.uint8, device=self.device)
-        group = g.to(self.device)
-        b = Go1ResponseBuffers()
-        b.trace, b.group = self.trace.data_ptr(), group.data_ptr()
-        b.results, b.values, b.status = out.data_ptr(), out.data_ptr() + nbytes[0], out.data_ptr() + nbytes[0] + nbytes[1]
-        self._check(self.lib.go1eval_response(ctypes.byref(c), ctypes.byref(b), self._stream()), "go1eval_response")
-        self._check(self.lib.go1eval_response_reduce(ctypes.byref(c), ctypes.byref(b), self._stream()), "go1eval_response_reduce")
-        host = out.cpu().numpy()
-        table = host[:nbytes[0]].view(np.float64).reshape(G, R, NUM_FIELDS)
-        values = host[nbytes[0]:nbytes[0] + nbytes[1]].view(np.float32).reshape(S, NUM_RESPONSE, K)
-        res = {name: {m: table[:, s * NUM_RESPONSE + i, :].copy() for i, m in enumerate(RESPONSE_METRICS)} for s, name in enumerate(names)}
-        res["groups"] = table[:, R - 1, :len(RESPONSE_GROUP_FIELDS)].copy()
+        c.switch_row, c.pre, c.smooth, c.hold, c.tail, c.band, c.dt = int(switch_row), int(pre), int(smooth), int(hold), int(tail), float(band), float(dt)
+        table, values, status = self._analysis(c, Go1ResponseBuffers, ("go1eval_response", "go1eval_response_reduce"), len(names) * NUM_RESPONSE, groups)
+        rows, values = table[:, :-1, :].reshape(-1, len(names), NUM_RESPONSE, NUM_FIELDS), values.reshape(len(names), NUM_RESPONSE, -1)
+        res = {name: {m: rows[:, s, i, :].copy() for i, m in enumerate(RESPONSE_METRICS)} for s, name in enumerate(names)}
+        res["groups"] = table[:, -1, :len(RESPONSE_GROUP_FIELDS)].copy()
         res["values"] = {name: {m: values[s, i].copy() for i, m in enumerate(RESPONSE_METRICS)} for s, name in enumerate(names)}
-        res["status"] = host[nbytes[0] + nbytes[1]:].view(np.int32).copy()
+        res["status"] = status
         return res
 
     def recovery(self, push_row, pre, smooth, band, hold, dt, groups):
@@ -502,48 +504,27 @@ class Go1Trace:
         "groups": (G, 5) array with the columns RECOVERY_GROUP_FIELDS, "values": {metric: (K,) float32} and "status": (K,) int32
         (RECOVERY_STATUS).  Two launches and one device-to-host copy."""
         assert self.trace is not None, "arm() first"
-        K = int(self.cfg.num_traced)
-        g = torch.as_tensor(groups).to(torch.int32).reshape(-1)
-        assert g.numel() == K, (g.numel(), K)
-        G = int(g.max()) + 1
-        assert G >= 1, "no traced environment carries a group id >= 0"
         c = Go1RecoveryConfig()
-        c.num_traced, c.rows, c.push_row, c.pre, c.smooth, c.hold = K, self.rows, int(push_row), int(pre), int(smooth), int(hold)
-        c.band, c.dt, c.num_groups = float(band), float(dt), G
-        R = NUM_RECOVERY + 1
-        nbytes = [G * R * NUM_FIELDS * 8, NUM_RECOVERY * K * 4, K * 4]                # results (fp64 first: aligned), values, status
-        out = torch.zeros(sum(nbytes), dtype=torch.uint8, device=self.device)
-        group = g.to(self.device)
-        b = Go1RecoveryBuffers()
-        b.trace, b.group = self.trace.data_ptr(), group.data_ptr()
-        b.results, b.values, b.status = out.data_ptr(), out.data_ptr() + nbytes[0], out.data_ptr() + nbytes[0] + nbytes[1]
-        self._check(self.lib.go1eval_recovery(ctypes.byref(c), ctypes.byref(b), self._stream()), "go1eval_recovery")
-        self._check(self.lib.go1eval_recovery_reduce(ctypes.byref(c), ctypes.byref(b), self._stream()), "go1eval_recovery_reduce")
-        host = out.cpu().numpy()
-        table = host[:nbytes[0]].view(np.float64).reshape(G, R, NUM_FIELDS)
-        values = host[nbytes[0]:nbytes[0] + nbytes[1]].view(np.float32).reshape(NUM_RECOVERY, K)
+        c.push_row, c.pre, c.smooth, c.hold, c.band, c.dt = int(push_row), int(pre), int(smooth), int(hold), float(band), float(dt)
+        table, values, status = self._analysis(c, Go1RecoveryBuffers, ("go1eval_recovery", "go1eval_recovery_reduce"), NUM_RECOVERY, groups)
         res = {m: table[:, i, :].copy() for i, m in enumerate(RECOVERY_METRICS)}
-        res["groups"] = table[:, R - 1, :len(RECOVERY_GROUP_FIELDS)].copy()
+        res["groups"] = table[:, -1, :len(RECOVERY_GROUP_FIELDS)].copy()
         res["values"] = {m: values[i].copy() for i, m in enumerate(RECOVERY_METRICS)}
-        res["status"] = host[nbytes[0] + nbytes[1]:].view(np.int32).copy()
+        res["status"] = status
         return res
 
 
-class Go1Push:
+class Go1Push(_Host):
     """Pushes of one simulator instance: a table of velocity steps (forward, left, up, yaw rate; PUSH_ROWS) for chosen environments,
     checked on the host, held on the device, and added to the base velocities in root_states by one launch per `launch()`.
     S: the simulator's Go1SimConfig, buffers: its SimBuffers (device tensors).  Nothing is allocated before the first load()."""
 
     def __init__(self, S, buffers, lib=None):
-        self.lib = lib if lib is not None else load_library()
-        self.buffers = buffers
-        self.device = buffers.device
+        super().__init__(buffers, lib)
         self.cfg = Go1PushConfig()
         self.cfg.num_envs = int(S.num_envs)
         self.buf = Go1PushBuffers()
         self.table = self.ids = self.env_ids = None
-
-    _stream, _check = Go1Eval._stream, Go1Eval._check
 
     def load(self, push, env_ids=None):
         """the table of the next launches: push (K, 4), one row of PUSH_ROWS per pushed environment; env_ids (K,) or None (every
@@ -561,13 +542,7 @@ class Go1Push:
                 raise ValueError(f"push: a table without environment ids needs one row per environment ({N}), not {K}")
             ids = None
         else:
-            ids = np.asarray(torch.as_tensor(env_ids).cpu(), dtype=np.int64).reshape(-1)
-            if ids.size != K:
-                raise ValueError(f"push: {ids.size} environment ids for {K} rows")
-            if ids.min() < 0 or ids.max() >= N:
-                raise ValueError(f"push: environment ids have to lie in [0, {N})")
-            if np.unique(ids).size != ids.size:
-                raise ValueError("push: an environment is named twice")
+            ids = _env_ids(env_ids, N, "push", rows=K)
         self.env_ids = np.arange(N, dtype=np.int32) if ids is None else ids.astype(np.int32)
         self.ids = None if ids is None else torch.from_numpy(self.env_ids).to(self.device)
         self.table = torch.from_numpy(np.ascontiguousarray(p.T)).to(self.device)              # [4][K]
@@ -580,25 +555,23 @@ class Go1Push:
     def launch(self):
         """add the loaded table to the base velocities now (one launch, no sync): between two simulator steps"""
         assert self.table is not None, "load() first"
-        self._check(self.lib.go1eval_push(ctypes.byref(self.cfg), ctypes.byref(self.buf), self._stream()), "go1eval_push")
+        self._launch("go1eval_push", self.cfg, self.buf)
 
 
-_TERRAIN_STATE_DTYPES = {"status": torch.uint8, "steps": torch.int32, "end_step": torch.int32, "max_dist": torch.float32}
-
-
-class Go1Terrain:
+class Go1Terrain(_Table):
     """Terrain traversal of one simulator instance, beside the tables: it owns its accumulators and the per-environment status,
     step count and distance, and binds the simulator's height field and env_origins.  S: the simulator's Go1SimConfig, buffers:
     its SimBuffers (device tensors), dt: the policy step in seconds, tile_length / tile_width: a tile's extent along x / y in
-    metres.  A simulator without a height field (the plane) gives height_samples = NULL: the ground is 0."""
+    metres.  A simulator without a height field (the plane) gives height_samples = NULL: the ground is 0.  clear() leaves every
+    environment RUNNING at step 0."""
+    PREFIX, CONFIG, BUFFERS, INPUTS = "go1eval_terrain", Go1TerrainConfig, Go1TerrainBuffers, _TERRAIN_INPUTS
+    ROWS, TABLE_ROWS = NUM_TERRAIN, NUM_TERRAIN + NUM_OUTCOME + 1
+    STATE = {"status": (torch.uint8, ()), "steps": (torch.int32, ()), "end_step": (torch.int32, ()), "max_dist": (torch.float32, ())}
 
     def __init__(self, S, buffers, dt, tile_length, tile_width, lib=None):
-        self.lib = lib if lib is not None else load_library()
-        self.buffers = buffers
-        self.device = buffers.device
-        N = self.num_envs = int(S.num_envs)
-        c = self.cfg = Go1TerrainConfig()
-        c.num_envs, c.dt, c.tile_length, c.tile_width = N, float(dt), float(tile_length), float(tile_width)
+        super().__init__(S, buffers, lib)
+        c = self.cfg
+        c.dt, c.tile_length, c.tile_width = float(dt), float(tile_length), float(tile_width)
         c.penalised_body_mask = int(S.penalised_body_mask)
         self.field = buffers.height_samples
         if self.field is not None:
@@ -606,59 +579,7 @@ class Go1Terrain:
             c.hf_hscale, c.hf_vscale, c.hf_border = float(S.hf_hscale), float(S.hf_vscale), float(S.hf_border)
         else:
             c.hf_rows, c.hf_cols, c.hf_hscale, c.hf_vscale, c.hf_border = 0, 0, 1.0, 0.0, 0.0          # not read: every sample is 0
-        self.acc = {n: torch.zeros(NUM_TERRAIN, N, dtype=dt_, device=self.device) for n, dt_ in _ACC_DTYPES.items()}
-        self.state = {n: torch.zeros(N, dtype=dt_, device=self.device) for n, dt_ in _TERRAIN_STATE_DTYPES.items()}
-        self.group = torch.full((N,), -1, dtype=torch.int32, device=self.device)
-        self.table = None
-        self.armed = False
-        self.buf = Go1TerrainBuffers()
         self._refresh()
-
-    def _refresh(self):
-        b, B = self.buf, self.buffers
-        for n in _TERRAIN_INPUTS:
-            setattr(b, n, getattr(B, n).data_ptr() if n != "height_samples" else None)
-        if self.field is not None:
-            b.height_samples = self.field.data_ptr()
-        for n, t in list(self.acc.items()) + list(self.state.items()):
-            setattr(b, n, t.data_ptr())
-        b.group = self.group.data_ptr()
-        b.results = self.table.data_ptr() if self.table is not None else None
-
-    _stream, _check = Go1Eval._stream, Go1Eval._check
-
-    def _call(self, name):
-        self._check(getattr(self.lib, name)(ctypes.byref(self.cfg), ctypes.byref(self.buf), self._stream()), name)
-
-    def clear(self):
-        """empty accumulators, every environment RUNNING at step 0 (one launch, no sync)"""
-        self._call("go1eval_terrain_clear")
-
-    def arm(self, groups, warmup_steps=0):
-        """start a measurement (as Go1Eval.arm): sets the groups, sizes the table and clears"""
-        g = torch.as_tensor(groups).to(torch.int32).reshape(-1)
-        assert g.numel() == self.num_envs, (g.numel(), self.num_envs)
-        G = int(g.max()) + 1
-        assert G >= 1, "no environment carries a group id >= 0"
-        self.group.copy_(g)
-        self.cfg.num_groups, self.cfg.warmup_steps = G, int(warmup_steps)
-        self.table = torch.zeros(G, NUM_TERRAIN + NUM_OUTCOME + 1, NUM_FIELDS, dtype=torch.float64, device=self.device)
-        self._refresh()
-        self.clear()
-        self.armed = True
-
-    def accumulate(self):
-        """after a step: advance every RUNNING environment and fold its step (one launch, no sync)"""
-        self._call("go1eval_terrain_accumulate")
-
-    def disarm(self):
-        self.armed = False
-
-    def reduce(self):
-        """the result table [G][NUM_TERRAIN + NUM_OUTCOME + 1][NUM_FIELDS] as a device tensor (one launch, no sync)"""
-        assert self.table is not None, "arm() first"
-        self._call("go1eval_terrain_reduce")
-        return self.table
 
     def read(self):
         """{"metrics": {name: (G, 6) array with the columns FIELD_NAMES}, "outcomes": {name: (G, 6) array}, "groups": (G, 6) array with
@@ -678,78 +599,39 @@ def joint_edges(limit):
     return float(limit) * (np.arange(JOINT_TAU_BINS + 1) / 4.0 - 1.0)
 
 
-class Go1Joints:
+class Go1Joints(_Table):
     """Per-joint actuator usage of one simulator instance, beside the tables: it owns its accumulators ([12 * 10][N]), its copy of the
     previous joint velocities and the per-environment torque-speed histogram ([12][64][N]).  S: the simulator's Go1SimConfig,
     buffers: its SimBuffers (device tensors), dt: the policy step in seconds, vel_limit: the twelve URDF speed limits in rad/s,
     soft_torque_limit / soft_vel_limit: the factors of the two saturation tests.  The torque limits and the soft position limits are
-    the simulator's own (S.torque_limits, S.dof_pos_soft_lower / upper)."""
+    the simulator's own (S.torque_limits, S.dof_pos_soft_lower / upper).  clear() also empties the histogram and takes the
+    simulator's current joint velocities as the previous ones."""
+    PREFIX, CONFIG, BUFFERS, INPUTS = "go1eval_joint", Go1JointConfig, Go1JointBuffers, _JOINT_INPUTS
+    ROWS, TABLE_ROWS = NUM_DOF * NUM_JOINT, NUM_DOF * NUM_JOINT + 1
+    STATE = {"prev_dof_vel": (torch.float32, (NUM_DOF,)), "steps": (torch.int32, ()), "resets": (torch.int32, ()),
+             "hist": (torch.int32, (NUM_DOF, JOINT_TAU_BINS * JOINT_VEL_BINS))}
 
     def __init__(self, S, buffers, dt, vel_limit, soft_torque_limit=1.0, soft_vel_limit=1.0, lib=None):
-        self.lib = lib if lib is not None else load_library()
-        self.buffers = buffers
-        self.device = buffers.device
-        N = self.num_envs = int(S.num_envs)
-        c = self.cfg = Go1JointConfig()
-        c.num_envs, c.dt, c.soft_torque_limit, c.soft_vel_limit = N, float(dt), float(soft_torque_limit), float(soft_vel_limit)
+        super().__init__(S, buffers, lib)
+        c = self.cfg
+        c.dt, c.soft_torque_limit, c.soft_vel_limit = float(dt), float(soft_torque_limit), float(soft_vel_limit)
         for j in range(NUM_DOF):
             c.torque_limit[j], c.vel_limit[j] = float(S.torque_limits[j]), float(vel_limit[j])
             c.pos_lower[j], c.pos_upper[j] = float(S.dof_pos_soft_lower[j]), float(S.dof_pos_soft_upper[j])
-        self.acc = {n: torch.zeros(NUM_DOF * NUM_JOINT, N, dtype=dt_, device=self.device) for n, dt_ in _ACC_DTYPES.items()}
-        self.state = dict(prev_dof_vel=torch.zeros(NUM_DOF, N, dtype=torch.float32, device=self.device),
-                          steps=torch.zeros(N, dtype=torch.int32, device=self.device), resets=torch.zeros(N, dtype=torch.int32, device=self.device),
-                          hist=torch.zeros(NUM_DOF, JOINT_TAU_BINS * JOINT_VEL_BINS, N, dtype=torch.int32, device=self.device))
-        self.group = torch.full((N,), -1, dtype=torch.int32, device=self.device)
-        self.table = self.hist_table = None
-        self.armed = False
-        self.buf = Go1JointBuffers()
+        self.hist_table = None
         self._refresh()
 
     def _refresh(self):
-        b, B = self.buf, self.buffers
-        for n in _JOINT_INPUTS:
-            setattr(b, n, getattr(B, n).data_ptr())
-        for n, t in list(self.acc.items()) + list(self.state.items()):
-            setattr(b, n, t.data_ptr())
-        b.group = self.group.data_ptr()
-        b.results = self.table.data_ptr() if self.table is not None else None
-        b.hist_results = self.hist_table.data_ptr() if self.hist_table is not None else None
+        super()._refresh()
+        self.buf.hist_results = self.hist_table.data_ptr() if self.hist_table is not None else None
 
-    _stream, _check = Go1Eval._stream, Go1Eval._check
-
-    def _call(self, name):
-        self._check(getattr(self.lib, name)(ctypes.byref(self.cfg), ctypes.byref(self.buf), self._stream()), name)
-
-    def clear(self):
-        """empty accumulators and histogram, the previous velocities = the simulator's current ones (one launch, no sync)"""
-        self._call("go1eval_joint_clear")
-
-    def arm(self, groups, warmup_steps=0):
-        """start a measurement (as Go1Eval.arm): sets the groups, sizes the two tables and clears"""
-        g = torch.as_tensor(groups).to(torch.int32).reshape(-1)
-        assert g.numel() == self.num_envs, (g.numel(), self.num_envs)
-        G = int(g.max()) + 1
-        assert G >= 1, "no environment carries a group id >= 0"
-        self.group.copy_(g)
-        self.cfg.num_groups, self.cfg.warmup_steps = G, int(warmup_steps)
-        self.table = torch.zeros(G, NUM_DOF * NUM_JOINT + 1, NUM_FIELDS, dtype=torch.float64, device=self.device)
+    def _size_tables(self, G):
+        super()._size_tables(G)
         self.hist_table = torch.zeros(G, NUM_DOF, JOINT_TAU_BINS, JOINT_VEL_BINS, dtype=torch.int64, device=self.device)   # (uint64 on the device)
-        self._refresh()
-        self.clear()
-        self.armed = True
-
-    def accumulate(self):
-        """after a step: fold the step of every joint (one launch, no sync)"""
-        self._call("go1eval_joint_accumulate")
-
-    def disarm(self):
-        self.armed = False
 
     def reduce(self):
         """(the result table [G][12 * 10 + 1][NUM_FIELDS], the histogram table [G][12][8][8]) as device tensors (one launch, no sync)"""
-        assert self.table is not None, "arm() first"
-        self._call("go1eval_joint_reduce")
-        return self.table, self.hist_table
+        return super().reduce(), self.hist_table
 
     def read(self):
         """{"metrics": {name: (G, 12, 6) array with the columns FIELD_NAMES, one row per joint of DOF_NAMES}, "groups": (G, 3) array with
