@@ -28,6 +28,22 @@ __device__ __forceinline__ bf16_t f2bf(float f) {          // round to nearest e
 }
 struct alignas(16) Bf8 { bf16_t v[8]; };
 
+// 16 bytes per lane, written THROUGH to memory (global_store_dwordx4 ... sc1), for outputs that are streamed out and not read again inside the
+// launch.  A plain store leaves its line dirty in the XCD's L2; what is still dirty at the end of the kernel (up to the L2s' 32 MB) is written
+// back while every CU idles and the dependent launch waits.  A write-through store costs what a plain one does at this width and drops the
+// line from the L2 (MI355X: narrower write-through stores cost 2.7x (8 B) to 6x (4 B) per byte: those stay plain).  p is 16-byte aligned.
+// Adopted kernel by kernel, in situ (profiles/store_paths_kernel_stats.txt): the first-layer ELU pass, mlp2_bwd's dz2 / dx rows and the weight
+// gradient's slab rows use it; the norm pass's sums (the Adam kernel reads those 13 MB back from the L2s: 3 us slower), the Adam kernel's
+// p / m / v, mlp2_fwd's activated input and the NT GEMM's epilogue gained nothing measurable and keep their plain stores.
+// (s_nop 1: the store reads its data registers over several cycles, and nothing the compiler places behind the statement may overwrite them)
+typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
+__device__ __forceinline__ void put16_wt(void* p, u32x4_t v) {
+  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"((__attribute__((address_space(1))) void*)p), "v"(v) : "memory");
+}
+__device__ __forceinline__ void put16_wt(void* p, const Bf8& v) { put16_wt(p, __builtin_bit_cast(u32x4_t, v)); }
+__device__ __forceinline__ void put16_wt(void* p, f32x4 v) { put16_wt(p, __builtin_bit_cast(u32x4_t, v)); }
+__device__ __forceinline__ void put16_wt(void* p, uint4 v) { put16_wt(p, u32x4_t{v.x, v.y, v.z, v.w}); }
+
 // ELU with alpha = 1.  exp(x) - 1 through the hardware exponential loses relative accuracy only for |x| < ~1e-3, where the
 // two-term series is exact to fp32; both are far inside the bf16 rounding of the stored activation.
 __device__ __forceinline__ float elu1(float x) {
@@ -107,7 +123,7 @@ __global__ __launch_bounds__(256) void elu_fwd_kernel(bf16_t* y, int rows, int c
     int r = r0 + u * 16;
 #pragma unroll
     for (int e = 0; e < 8; e++) x[u][e] = elu1(x[u][e]);
-    if (r < rows) *reinterpret_cast<Bf8*>(y + (int64_t)r * ld + c0) = pack_bf8(x[u]);
+    if (r < rows) put16_wt(y + (int64_t)r * ld + c0, pack_bf8(x[u]));       // (in place: this lane alone loaded these 16 bytes, above)
   }
 }
 

@@ -296,13 +296,13 @@ extern "C" int go1ppo_gemm_nt(const Go1PpoGemmArgs* a, void* stream) {
 //     slots (tools/probes/tr_bank_probe.hip: same rate as a contiguous image);
 //   * each wave owns 64 (n) x 32 (k): 4 x 2 accumulators of v_mfma_f32_16x16x32_bf16;
 //   * the reduction is split over row chunks (the output has only (n/128)(k/128) tiles).  The partial tiles go to per-chunk fp32 SLABS
-//     (Go1PpoWgradProblem.partials, plain stores; summed in a fixed order by the optimiser's norm pass or go1ppo_grad_reduce) — or, without
+//     (Go1PpoWgradProblem.partials, whole rows written through: wtn_slab_rows; summed in a fixed order by the optimiser's norm pass or go1ppo_grad_reduce) — or, without
 //     slabs, meet in fp32 atomics on the gradient buffer itself (~200 G atomic adds/s chip-wide: 15.6 of the 64.5 us of the PPO pass's
 //     launch, which is why the product path uses slabs); the bias gradient (column sums of dZ) is one more MFMA per fragment against a
 //     fragment of ones, in the workgroups of the first column tile, stored write-through (16-B sc1 stores) as the row chunk's row of a
 //     bias slab and summed in chunk order by the last of those workgroups (det_last, go1ppo.hip): the same bias gradient in every run.
-//     No release fence: it would write back the whole XCD L2, the weight-slab tiles included, which stay plain stores (the next
-//     kernel reads them, and the kernel boundary orders them).
+//     No release fence: it would write back the whole XCD L2; the weight-slab tiles are written through as well and are drained by the
+//     same vmcnt(0) in front of the ticket (the next kernel reads them, and the kernel boundary orders them).
 // rows % 64 == 0, n % 8 == 0, k % 8 == 0.
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;
 typedef __attribute__((ext_vector_type(8))) short s16x8_t;
@@ -346,6 +346,40 @@ __device__ __forceinline__ bf16x8_t tn_operand(const TnFrags& f, int i) {
 #define WTN_STEP 64          // reduction rows per step
 #define WTN_BUFS 4           // LDS buffers: WTN_BUFS - 1 steps in flight
 #define WTN_THREADS 512
+
+// ---- slab epilogue of both tile bodies.  The accumulator layout (a lane: 4 consecutive n of ONE k) gives 4-byte stores in 64-byte runs, from all
+// 256 workgroups at the same moment (the planner equalises the chunks), and leaves the tiles dirty in the L2s for the end-of-kernel write-back.
+// Instead the finished tile goes through the LDS the staging buffers occupied, as an image [n][128 k] fp32 (512-byte rows), and leaves as whole
+// rows: 32 lanes x 16 bytes, written through (put16_wt, go1ppo.hip).  The 16-byte chunk index is XOR-ed with 4 ((n >> 2) & 3): the four n a
+// store instruction's lane groups hold (4 rows apart, the same banks) land in four different 64-byte bank groups, and a row read stays a
+// permutation of its 32 chunks.  Needs 16-byte aligned slab rows (the flat gradient's offsets, strides and widths are multiples of 8).
+__device__ __forceinline__ bool wtn_rows_ok(bool slab, const float* C, int ldc) { return slab && !(ldc & 3) && !((uintptr_t)C & 15); }
+__device__ __forceinline__ int wtn_img_chunk(int row, int chunk) { return chunk ^ (((row >> 2) & 3) << 2); }
+__device__ __forceinline__ void wtn_img_put(float* img, int row, int col, float x) {
+  img[row * WTN_T + (wtn_img_chunk(row, col >> 2) << 2) + (col & 3)] = x;
+}
+// rows n0 .. n0 + ROWS - 1 of the image to C[n][k0 ..]: the n < N, k < K edges (K % 8 == 0: a 4-column group is in or out as a whole) and the
+// structural-zero block are skipped as the element-wise stores skip them; a group the block cuts goes out value by value (det_put: written
+// through as well, so no line of the slab is part dirty in the L2, part written through)
+template <int ROWS>
+__device__ __forceinline__ void wtn_slab_rows(const float* img, float* C, int ldc, int N, int K, int n0, int k0, int zero_n, int zero_k0,
+                                              int zero_k1) {
+  const int chunk = threadIdx.x & 31, k = k0 + 4 * chunk;
+  if (k >= K) return;
+#pragma unroll
+  for (int it = 0; it < ROWS / (WTN_THREADS / 32); it++) {
+    const int row = (int)(threadIdx.x >> 5) + (WTN_THREADS / 32) * it, n = n0 + row;
+    if (n >= N) continue;
+    const f32x4 v = *reinterpret_cast<const f32x4*>(img + row * WTN_T + (wtn_img_chunk(row, chunk) << 2));
+    float* dst = C + (int64_t)n * ldc + k;
+    if (!(n < zero_n && k < zero_k1 && k + 4 > zero_k0)) put16_wt(dst, v);
+    else {
+#pragma unroll
+      for (int e = 0; e < 4; e++)
+        if (!(k + e >= zero_k0 && k + e < zero_k1)) det_put(dst + e, v[e]);
+    }
+  }
+}
 
 __device__ __forceinline__ void wgrad_tn_body(const bf16_t* P, int ldp, const bf16_t* Q, int ldq, int64_t m_begin, int steps,
                                               float* C, int ldc, float* bias_row, int N, int K, int n0, int k0,
@@ -448,17 +482,29 @@ __device__ __forceinline__ void wgrad_tn_body(const bf16_t* P, int ldp, const bf
     }
   }
   // ---- lane holds D[n = 4g + e][k = i16] of each fragment pair
+  if (wtn_rows_ok(slab, C, ldc)) {                                // (uniform) this row chunk's slab tile, as whole rows
+    float* img = reinterpret_cast<float*>(&lds[0][0][0]);
+    __syncthreads();                                              // every wave has read its last fragments: the staging buffers are free
+#pragma unroll
+    for (int a = 0; a < 4; a++)
+#pragma unroll
+      for (int e = 0; e < 4; e++)
+#pragma unroll
+        for (int b = 0; b < 2; b++) wtn_img_put(img, wn * 64 + a * 16 + 4 * g + e, wk * 32 + b * 16 + i16, acc[a][b][e]);
+    __syncthreads();
+    wtn_slab_rows<WTN_T>(img, C, ldc, N, K, n0, k0, zero_n, zero_k0, zero_k1);
+  }
 #pragma unroll
   for (int a = 0; a < 4; a++) {
 #pragma unroll
     for (int e = 0; e < 4; e++) {
       const int n = n0 + wn * 64 + a * 16 + 4 * g + e;
-      if (n >= N) continue;
+      if (n >= N || wtn_rows_ok(slab, C, ldc)) continue;
 #pragma unroll
       for (int b = 0; b < 2; b++) {
         const int k = k0 + wk * 32 + b * 16 + i16;
         if (k < K && !(n < zero_n && k >= zero_k0 && k < zero_k1)) {
-          if (slab) C[(int64_t)n * ldc + k] = acc[a][b][e];           // this row chunk's slab (Go1PpoWgradProblem.partials): summed by the reduction pass
+          if (slab) C[(int64_t)n * ldc + k] = acc[a][b][e];           // a slab whose rows are not 16-byte aligned: element by element
           else atomicAdd(C + (int64_t)n * ldc + k, acc[a][b][e]);
         }
       }
@@ -592,12 +638,24 @@ __device__ __forceinline__ void wgrad_tn_body_wide(const bf16_t* P, int ldp, con
     buf = buf + 1 == WTW_BUFS ? 0 : buf + 1;
   }
   // ---- lane holds D[n = 4g + e][k = i16] of each fragment pair
+  if (wtn_rows_ok(slab, C, ldc)) {                                // (uniform) this row chunk's slab tile, as whole rows
+    float* img = reinterpret_cast<float*>(lds);                   // 256 x 128 fp32 = 128 of the 144 KB
+    __syncthreads();                                              // every wave has read its last fragments: the staging buffers are free
+#pragma unroll
+    for (int a = 0; a < 4; a++)
+#pragma unroll
+      for (int e = 0; e < 4; e++)
+#pragma unroll
+        for (int b = 0; b < 4; b++) wtn_img_put(img, wn * 64 + a * 16 + 4 * g + e, wk * 64 + b * 16 + i16, acc[a][b][e]);
+    __syncthreads();
+    wtn_slab_rows<2 * WTN_T>(img, C, ldc, N, K, n0, k0, zero_n, zero_k0, zero_k1);
+  }
 #pragma unroll
   for (int a = 0; a < 4; a++) {
 #pragma unroll
     for (int e = 0; e < 4; e++) {
       const int n = n0 + wn * 64 + a * 16 + 4 * g + e;
-      if (n >= N) continue;
+      if (n >= N || wtn_rows_ok(slab, C, ldc)) continue;
 #pragma unroll
       for (int b = 0; b < 4; b++) {
         const int k = k0 + wk * 64 + b * 16 + i16;

@@ -281,11 +281,12 @@ __global__ __launch_bounds__(MLP2_THREADS, 1) void mlp2_bwd_kernel(Mlp2BwdArgs A
     }
     __syncthreads();
     // ---- the finished tiles leave row by row
-    if (row0 + zrow < N.rows) *reinterpret_cast<uint4*>(dz2 + (row0 + zrow) * N.ld_dz2 + zch * 8) = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(D2i) + zslot);
+    // (written through, go1ppo.hip put16_wt; dz2 / dx may be the z2 / h buffers: a tile's rows are fetched by these same lanes, a tile ahead)
+    if (row0 + zrow < N.rows) put16_wt(dz2 + (row0 + zrow) * N.ld_dz2 + zch * 8, *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(D2i) + zslot));
 #pragma unroll
     for (int j = 0; j < 2; j++)
       if (row0 + MLP2_HROW(j) < N.rows)
-        *reinterpret_cast<uint4*>(dx + (row0 + MLP2_HROW(j)) * N.ld_dx + hch * 8) = *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(Hi) + MLP2_HSLOT(j));
+        put16_wt(dx + (row0 + MLP2_HROW(j)) * N.ld_dx + hch * 8, *reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(Hi) + MLP2_HSLOT(j)));
     __syncthreads();                                                      // before the next tile's rows overwrite D2i / Hi
   }
 }
