@@ -284,6 +284,42 @@ typedef struct {
 } Go1PpoMlp2Bwd;
 int go1ppo_mlp2_bwd(const Go1PpoMlp2Bwd* nets, int count, void* stream);
 
+/* ---- forward, loss and backward of the 256 -> 128 -> 64 ends as ONE launch per pass ----
+ * A 64-row tile stays on chip from x to d_x: what go1ppo_mlp2_fwd + go1ppo_loss (or go1ppo_mse) + go1ppo_mlp2_bwd compute,
+ * bit for bit, sums included.  d_z2 / d_x must not be the z2 / x buffers. */
+typedef struct {
+  void* x;                     /* as Go1PpoMlp2Fwd.x (activated in place when elu_input != 0): the backward pass's h */
+  const void* W2; const void* b2;
+  const void* W3; const void* b3;
+  void* z2;                    /* out: as Go1PpoMlp2Fwd.z2 */
+  void* out;                   /* out: as Go1PpoMlp2Fwd.out — the loss's mean / value / pred */
+  void* d_out;                 /* in/out: bf16 [rows][ld_dout]: the loss writes its columns, the others are read as they are */
+  void* d_z2;                  /* out: as Go1PpoMlp2Bwd.d_z2 */
+  void* d_x;                   /* out: as Go1PpoMlp2Bwd.d_x */
+  int64_t rows;
+  int32_t ld_x, ld_z2, ld_out, ld_dout, ld_dz2, ld_dx, elu_input, _pad;
+} Go1PpoMlp2Tail;
+
+#define GO1PPO_TAIL_MAX_ACTIONS 12
+/* nets[0] = actor, nets[1] = critic, equal row counts.  `loss` as for go1ppo_loss with mean / value / d_mean / d_value equal to the nets'
+ * out / d_out, rows equal to the nets' and head_ld == ld_out == ld_dout == 64.
+ * Returns -1: a null pointer, rows <= 0, or num_actions outside 1 .. GO1PPO_TAIL_MAX_ACTIONS (larger heads: the three launches);
+ * -2: a leading dimension, an alignment or one of the equalities above (checked after the -1 conditions). */
+int go1ppo_mlp2_tail_ppo(const Go1PpoMlp2Tail* nets, const Go1PpoLossArgs* loss, void* stream);
+
+typedef struct {
+  const float* target;         /* fp32 storage [.][npv], gathered through idx */
+  const int64_t* idx;          /* int64 [rows] */
+  int64_t num_train;
+  int32_t npv, selective;
+  float* d_pred_bias;          /* [npv] += (may be NULL, as the losses) */
+  float* train_loss;           /* [1] += */
+  float* test_loss;            /* [1] += */
+} Go1PpoMseArgs;
+/* One net; pred = net->out, d_pred = net->d_out, pred_ld = ld_out == ld_dout == 64: go1ppo_mse in the middle.
+ * Returns -1: a null pointer, rows <= 0, num_train outside 1 .. rows - 1, npv outside 1 .. 64; -2: as above. */
+int go1ppo_mlp2_tail_mse(const Go1PpoMlp2Tail* net, const Go1PpoMseArgs* mse, void* stream);
+
 const char* go1ppo_version(void);
 
 #ifdef __cplusplus

@@ -78,7 +78,18 @@ class Mlp2Bwd(ctypes.Structure):
                [(n, ctypes.c_int32) for n in ("ld_dout", "ld_z2", "ld_h", "ld_dz2", "ld_dx", "_pad")]
 
 
+class Mlp2Tail(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("x", "W2", "b2", "W3", "b3", "z2", "out", "d_out", "d_z2", "d_x")] + [("rows", ctypes.c_int64)] + \
+               [(n, ctypes.c_int32) for n in ("ld_x", "ld_z2", "ld_out", "ld_dout", "ld_dz2", "ld_dx", "elu_input", "_pad")]
+
+
+class MseArgs(ctypes.Structure):
+    _fields_ = [("target", ctypes.c_void_p), ("idx", ctypes.c_void_p), ("num_train", ctypes.c_int64), ("npv", ctypes.c_int32),
+                ("selective", ctypes.c_int32), ("d_pred_bias", ctypes.c_void_p), ("train_loss", ctypes.c_void_p), ("test_loss", ctypes.c_void_p)]
+
+
 MLP2_DIMS = (256, 128, 64)
+TAIL_MAX_ACTIONS = 12          # GO1PPO_TAIL_MAX_ACTIONS
 
 
 class GemmArgs(ctypes.Structure):
@@ -95,7 +106,7 @@ class AdamExtras(ctypes.Structure):
     _fields_ = [("num_transposes", ctypes.c_int32), ("_pad", ctypes.c_int32), ("transpose", _AdamTranspose * 2)]
 
 
-EXPORTED_SYMBOLS = ["go1ppo_mlp2_fwd", "go1ppo_mlp2_bwd", "go1ppo_gemm_nt", "go1ppo_gemm_nt_pair", "go1ppo_sum_partials", "go1ppo_wgrad_tn_plan", "go1ppo_wgrad_tn_batched", "go1ppo_tail_fwd", "go1ppo_elu_fwd", "go1ppo_elu_bwd", "go1ppo_loss", "go1ppo_mse", "go1ppo_wgrad", "go1ppo_wgrad_plan",
+EXPORTED_SYMBOLS = ["go1ppo_mlp2_fwd", "go1ppo_mlp2_bwd", "go1ppo_mlp2_tail_ppo", "go1ppo_mlp2_tail_mse", "go1ppo_gemm_nt", "go1ppo_gemm_nt_pair", "go1ppo_sum_partials", "go1ppo_wgrad_tn_plan", "go1ppo_wgrad_tn_batched", "go1ppo_tail_fwd", "go1ppo_elu_fwd", "go1ppo_elu_bwd", "go1ppo_loss", "go1ppo_mse", "go1ppo_wgrad", "go1ppo_wgrad_plan",
                     "go1ppo_wgrad_batched", "go1ppo_act",
                     "go1ppo_store_step", "go1ppo_ring_snapshot", "go1ppo_ring_step", "go1ppo_ring_gather", "go1ppo_gae", "go1ppo_normalize", "go1ppo_opt_partials", "go1ppo_opt_prestep",
                     "go1ppo_opt_prestep_pieces", "go1ppo_grad_reduce", "go1ppo_opt_adam", "go1ppo_version"]
@@ -124,6 +135,8 @@ def load_library(path=None):
     L.go1ppo_sum_partials.argtypes = [vp, i32, i64, i64, i32, vp, i32, i32, i32, vp]
     L.go1ppo_mlp2_fwd.argtypes = [ctypes.POINTER(Mlp2Fwd), i32, vp]
     L.go1ppo_mlp2_bwd.argtypes = [ctypes.POINTER(Mlp2Bwd), i32, vp]
+    L.go1ppo_mlp2_tail_ppo.argtypes = [ctypes.POINTER(Mlp2Tail), ctypes.POINTER(LossArgs), vp]
+    L.go1ppo_mlp2_tail_mse.argtypes = [ctypes.POINTER(Mlp2Tail), ctypes.POINTER(MseArgs), vp]
     L.go1ppo_wgrad_batched.argtypes = [vp, i32, i32, vp]
     L.go1ppo_wgrad_tn_plan.argtypes = [ctypes.POINTER(WgradProblem), i32]
     L.go1ppo_wgrad_tn_batched.argtypes = [vp, i32, i32, vp]
@@ -255,6 +268,9 @@ class FusedNet:
                           and tuple(self.P[f"{n}.{self.depth[n] - 1}.W"].shape) == (MLP2_DIMS[2], MLP2_DIMS[1]) for n in self.depth)
                       and self.depth["adaptation"] == 3 and self.depth["actor"] == 4 and self.depth["critic"] == 4)
         self._mlp2_cache = {}
+        # set by the owner around forward / loss / backward of a pass whose MLP ends, loss and backward are one launch (`tail_ppo_fused`,
+        # `tail_adaptation_fused`): forward and backward then leave the ends to the loss call
+        self._tail_in_loss = False
         # (the first-layer forward stays on hipBLASLt: 96 us = 1.39 PFLOP/s in situ.  A 256-tile LDS-DMA GEMM of this repository with the ELU in
         #  its epilogue measured 135-140 us — bound by the L2 -> LDS staging rate of ~10.5 TB/s chip-wide, tools/probes/gemm256_probe.hip,
         #  DESIGN.md section 7 — and was withdrawn)
@@ -421,6 +437,45 @@ class FusedNet:
         arr, n = self._mlp2_cache[key]
         _chk(self.lib.go1ppo_mlp2_bwd(arr, n, _stream()), "go1ppo_mlp2_bwd")
 
+    def _mlp2_tail(self, key, items):
+        """items: [(net, x, d_x)] as for `_mlp2_fwd` / `_mlp2_bwd`: the Go1PpoMlp2Tail table of the one-launch form"""
+        key = ("tail", key)
+        if key not in self._mlp2_cache:
+            arr = (Mlp2Tail * len(items))()
+            for a, (net, x, d_x) in zip(arr, items):
+                d = self.depth[net]
+                W2, W3, z2, out = self.P[f"{net}.{d - 2}.W"], self.P[f"{net}.{d - 1}.W"], self.Z[net][d - 2], self.Z[net][d - 1]
+                d_out, d_z2 = self.dZ[net][d - 1], self.dZ[net][d - 2]
+                a.x, a.W2, a.b2, a.W3, a.b3 = x.data_ptr(), W2.data_ptr(), self.P[f"{net}.{d - 2}.b"].data_ptr(), W3.data_ptr(), self.P[f"{net}.{d - 1}.b"].data_ptr()
+                a.z2, a.out, a.d_out, a.d_z2, a.d_x, a.rows = z2.data_ptr(), out.data_ptr(), d_out.data_ptr(), d_z2.data_ptr(), d_x.data_ptr(), x.shape[0]
+                a.ld_x, a.ld_z2, a.ld_out, a.ld_dout, a.ld_dz2, a.ld_dx, a.elu_input = _ld(x), _ld(z2), _ld(out), _ld(d_out), _ld(d_z2), _ld(d_x), 1
+            self._mlp2_cache[key] = arr
+        return self._mlp2_cache[key]
+
+    def _tail_ok(self, arr):
+        """the preconditions of go1ppo_mlp2_tail_ppo / _mse on the nets' buffers (64-column heads, 16-byte aligned rows, no aliasing);
+        otherwise the pass keeps its three launches"""
+        for a in arr:
+            if a.ld_out != HEAD or a.ld_dout != HEAD or a.ld_x % 8 or a.ld_z2 % 8 or a.ld_dz2 % 8 or a.ld_dx % 8 or a.d_x == a.x or a.d_z2 == a.z2:
+                return False
+            if any(p % 16 for p in (a.x, a.W2, a.W3, a.z2, a.out, a.d_out, a.d_z2, a.d_x)) or a.b2 % 8 or a.b3 % 8:
+                return False
+        return True
+
+    def tail_ppo_fused(self, num_actions):
+        """True when forward + ppo_loss + backward of this engine run the actor's and critic's 256 -> 128 -> 64 ends, the loss and their
+        backward as ONE launch (issued by `ppo_loss`)"""
+        if not (self._mlp2 and self.G is not None and 0 < num_actions <= TAIL_MAX_ACTIONS):
+            return False
+        Z, dZ = self.Z, self.dZ
+        return self._tail_ok(self._mlp2_tail("ac", [("actor", Z["actor"][1], dZ["actor"][1]), ("critic", Z["critic"][1], dZ["critic"][1])]))
+
+    def tail_adaptation_fused(self):
+        """the same for forward_adaptation + adaptation_loss + backward_adaptation"""
+        if not (self._mlp2 and self.G is not None):
+            return False
+        return self._tail_ok(self._mlp2_tail("adaptation_only", [("adaptation", self.Y1d, self.dH1["adaptation"])]))
+
     def _forward_mlp2(self, x):
         P, Z, nd, na = self.P, self.Z, self.nd, self.na
         torch.mm(x, P["W1"].t(), out=self.Y1)
@@ -441,14 +496,16 @@ class FusedNet:
                 torch.addmm(P["critic.1.b"], self.Y1[:, nd + na:], P["critic.1.W"].t(), out=Z["critic"][1])
             torch.addmm(P["actor.1.b"], self.Y1[:, nd:nd + na], P["actor.1.W"].t(), out=Z["actor"][1])
         self._join()
-        self._mlp2_fwd("ac", [("actor", Z["actor"][1]), ("critic", Z["critic"][1])])
+        if not self._tail_in_loss:                  # (otherwise `ppo_loss` runs the ends forward, the loss and the ends backward as one launch)
+            self._mlp2_fwd("ac", [("actor", Z["actor"][1]), ("critic", Z["critic"][1])])
         return Z["actor"][3], Z["critic"][3], latent
 
     def _backward_mlp2(self, x):
         nd, na = self.nd, self.na
         P, G, Z, dZ, Y1, dY1, dH1 = self.P, self.G, self.Z, self.dZ, self.Y1, self.dY1, self.dH1
         cols = {"adaptation": slice(0, nd), "actor": slice(nd, nd + na), "critic": slice(nd + na, self.n1)}
-        self._mlp2_bwd("ac", [("actor", Z["actor"][1], dZ["actor"][1]), ("critic", Z["critic"][1], dZ["critic"][1])])
+        if not self._tail_in_loss:
+            self._mlp2_bwd("ac", [("actor", Z["actor"][1], dZ["actor"][1]), ("critic", Z["critic"][1], dZ["critic"][1])])
         for net in ("actor", "critic"):                     # the loss kernel already produced the heads' bias gradients
             self._wgrad(dZ[net][3], Z[net][2], G[f"{net}.3.W"], None)
             self._wgrad(dZ[net][2], Z[net][1], G[f"{net}.2.W"], G[f"{net}.2.b"])
@@ -486,12 +543,14 @@ class FusedNet:
 
     def _forward_adaptation_mlp2(self, x):
         torch.mm(x, self.P["W1"][:self.nd].t(), out=self.Y1d)
-        self._mlp2_fwd("adaptation_only", [("adaptation", self.Y1d)])
+        if not self._tail_in_loss:
+            self._mlp2_fwd("adaptation_only", [("adaptation", self.Y1d)])
         return self.Z["adaptation"][2]
 
     def _backward_adaptation_mlp2(self, x):
         nd, d, G, Z, dZ = self.nd, self.dH1["adaptation"], self.G, self.Z, self.dZ
-        self._mlp2_bwd("adaptation_only", [("adaptation", self.Y1d, d)])
+        if not self._tail_in_loss:
+            self._mlp2_bwd("adaptation_only", [("adaptation", self.Y1d, d)])
         self._wgrad(dZ["adaptation"][2], Z["adaptation"][1], G["adaptation.2.W"], None)     # head bias: the MSE kernel's
         self._wgrad(dZ["adaptation"][1], self.Y1d, G["adaptation.1.W"], G["adaptation.1.b"])
         self._big_wgrad(d, x, G["W1"][:nd], self._w1_tmp[:, :nd], own_kernel=self._wgrad_tn)
@@ -715,6 +774,11 @@ class FusedNet:
         a.kl = kl.data_ptr()
         a.value_loss = acc[0:].data_ptr()
         a.surrogate_loss = acc[1:].data_ptr()
+        if self._tail_in_loss:
+            Z, dZ = self.Z, self.dZ
+            arr = self._mlp2_tail("ac", [("actor", Z["actor"][1], dZ["actor"][1]), ("critic", Z["critic"][1], dZ["critic"][1])])
+            _chk(self.lib.go1ppo_mlp2_tail_ppo(arr, ctypes.byref(a), _stream()), "go1ppo_mlp2_tail_ppo")
+            return
         _chk(self.lib.go1ppo_loss(ctypes.byref(a), _stream()), "go1ppo_loss")
 
     def adaptation_loss(self, st, idx, num_train, selective, acc):
@@ -722,6 +786,13 @@ class FusedNet:
         pred, dpred = self.Z["adaptation"][last], self.dZ["adaptation"][last]
         target = st.privileged_observations.flatten(0, 1)
         assert target.is_contiguous() and target.dtype == torch.float32 and target.shape[1] == self.pol.npv
+        if self._tail_in_loss:
+            arr = self._mlp2_tail("adaptation_only", [("adaptation", self.Y1d, self.dH1["adaptation"])])
+            q = MseArgs()
+            q.target, q.idx, q.num_train, q.npv, q.selective = target.data_ptr(), idx.data_ptr(), num_train, self.pol.npv, int(selective)
+            q.d_pred_bias, q.train_loss, q.test_loss = self.G[f"adaptation.{last}.b"].data_ptr(), acc[2:].data_ptr(), acc[3:].data_ptr()
+            _chk(self.lib.go1ppo_mlp2_tail_mse(arr, ctypes.byref(q), _stream()), "go1ppo_mlp2_tail_mse")
+            return
         _chk(self.lib.go1ppo_mse(pred.data_ptr(), HEAD, target.data_ptr(), self.pol.npv, idx.data_ptr(), self.M, num_train,
                                  int(selective), dpred.data_ptr(), self.G[f"adaptation.{last}.b"].data_ptr(),
                                  acc[2:].data_ptr(), acc[3:].data_ptr(), _stream()), "go1ppo_mse")

@@ -442,9 +442,14 @@ class PPO:
                 self._gather_rows(idx, net.X)
             # (the flat gradient and the KL slot are clean here: update() clears them once, every fused optimiser step
             # clears what it has consumed)
-            net.forward(net.X)
-            net.ppo_loss(self.storage, idx, self.std, self.master.grad[n:n + self.n_std], PPO_Args, self._kl, self._acc)
-            net.backward(net.X)
+            # (large-batch engine: the actor's and critic's MLP ends forward, the loss and the ends backward are one launch, issued by ppo_loss)
+            net._tail_in_loss = net.tail_ppo_fused(self.std.numel())
+            try:
+                net.forward(net.X)
+                net.ppo_loss(self.storage, idx, self.std, self.master.grad[n:n + self.n_std], PPO_Args, self._kl, self._acc)
+                net.backward(net.X)
+            finally:
+                net._tail_in_loss = False
             # (the privileged-observation columns of the adaptation module's and the actor's first-layer rows — structurally zero
             #  weights — receive no gradient: masked by go1ppo_sum_partials / the batched weight-gradient launch, no fill pass)
 
@@ -460,9 +465,13 @@ class PPO:
         net = self._train_net          # net.X still holds this mini-batch's rows (gathered by the PPO stage)
         num_train = int(idx.numel() // 5 * 4)
         with torch.no_grad():
-            net.forward_adaptation(net.X)
-            net.adaptation_loss(self.storage, idx, num_train, PPO_Args.selective_adaptation_module_loss, self._acc)
-            net.backward_adaptation(net.X)
+            net._tail_in_loss = net.tail_adaptation_fused()
+            try:
+                net.forward_adaptation(net.X)
+                net.adaptation_loss(self.storage, idx, num_train, PPO_Args.selective_adaptation_module_loss, self._acc)
+                net.backward_adaptation(net.X)
+            finally:
+                net._tail_in_loss = False
 
     def _stage_ppo_backward(self, idx):
         """PPO loss forward + backward into the fp32 master gradient (reference ppo.py:112-155)."""
