@@ -46,14 +46,15 @@ typedef struct {
   const float* old_logp;     /* [.] */
   const float* advantages;   /* [.] */
   const float* returns;      /* [.] */
-  const float* old_values;   /* [.] */
+  const float* old_values;   /* [.]  (read only when use_clipped_value_loss != 0: may be NULL otherwise) */
   /* hyper-parameters (PPO_Args) */
   float clip_param, value_loss_coef, entropy_coef;
   int32_t use_clipped_value_loss;
-  /* outputs */
+  /* outputs: the two per-sample gradients are required; each of the six sums below them may be NULL (it is then not computed into
+   * anything, and the other outputs are what they are with it present) */
   void* d_mean;              /* [rows][head_ld] bf16: d loss / d mean   (columns >= num_actions untouched) */
   void* d_value;             /* [rows][head_ld] bf16: d loss / d value  (columns >= 1 untouched) */
-  float* d_std;              /* [num_actions]  += */
+  float* d_std;              /* [num_actions]  += (with the entropy term) */
   float* d_mean_bias;        /* [num_actions]  += column sums of d_mean */
   float* d_value_bias;       /* [1]            += */
   float* kl;                 /* [1] += mean KL(old || new) */
@@ -61,12 +62,18 @@ typedef struct {
   float* surrogate_loss;     /* [1] += */
 } Go1PpoLossArgs;
 
-/* Surrogate + clipped value + entropy loss of ppo.py:112-150, forward and analytic gradient in one pass. */
+/* Surrogate + clipped value + entropy loss of ppo.py:112-150, forward and analytic gradient in one pass.
+ * Returns -1, before any launch: args NULL; rows <= 0 or more than 2^20; num_actions outside 1 .. GO1PPO_MAX_ACTIONS; head_ld <
+ * num_actions; a NULL mean, value, std, idx, actions, old_mu, old_sigma, old_logp, advantages, returns, d_mean or d_value; a NULL
+ * old_values with use_clipped_value_loss != 0.  d_std, d_mean_bias, d_value_bias, kl, value_loss and surrogate_loss may each be NULL. */
 int go1ppo_loss(const Go1PpoLossArgs* args, void* stream);
 
 /* Adaptation-module regression (ppo.py:163-190): mse(pred[:num_train, sel], target[:num_train, sel]) and its
  * gradient; the remaining rows only feed the test loss.  pred: bf16 [rows][pred_ld]; target: fp32 storage
- * [.][npv] gathered through idx; selective != 0 -> column 0 only. */
+ * [.][npv] gathered through idx; selective != 0 -> column 0 only.  d_pred: bf16 [rows][pred_ld], columns < npv written (zeros in the
+ * test rows and, with selective, in columns 1 .. npv - 1), the others untouched; d_pred_bias [npv or 1] +=, train_loss / test_loss [1] +=.
+ * Returns -1, before any launch: a NULL pred, target, idx, d_pred, train_loss or test_loss; rows <= 0 or more than 2^20; num_train
+ * outside 1 .. rows - 1; npv outside 1 .. min(pred_ld, 64).  d_pred_bias may be NULL. */
 int go1ppo_mse(const void* pred, int pred_ld, const float* target, int npv, const int64_t* idx, int64_t rows,
                int64_t num_train, int selective, void* d_pred, float* d_pred_bias, float* train_loss,
                float* test_loss, void* stream);
@@ -312,9 +319,9 @@ typedef struct {
   const int64_t* idx;          /* int64 [rows] */
   int64_t num_train;
   int32_t npv, selective;
-  float* d_pred_bias;          /* [npv] += (may be NULL, as the losses) */
-  float* train_loss;           /* [1] += */
-  float* test_loss;            /* [1] += */
+  float* d_pred_bias;          /* [npv] += (may be NULL) */
+  float* train_loss;           /* [1] += (required) */
+  float* test_loss;            /* [1] += (required) */
 } Go1PpoMseArgs;
 /* One net; pred = net->out, d_pred = net->d_out, pred_ld = ld_out == ld_dout == 64: go1ppo_mse in the middle.
  * Returns -1: a null pointer, rows <= 0, num_train outside 1 .. rows - 1, npv outside 1 .. 64; -2: as above. */

@@ -158,9 +158,11 @@ def ppo_case(lib, rows, A, clipped):
     assert lib.go1ppo_mlp2_bwd(arr(F.Mlp2Bwd, [o_actor.bwd(F), o_critic.bwd(F)]), 2, stream()) == 0
     torch.cuda.synchronize()
 
-    def fused_run():
+    def fused_run(null=()):
         a, c, d = actor.clone(), critic.clone(), dests()
         la = loss_args(a, c, d)
+        for name in null:                                          # optional outputs passed as null pointers
+            setattr(la, name, None)
         rc = lib.go1ppo_mlp2_tail_ppo(arr(F.Mlp2Tail, [a.tail(F), c.tail(F)]), ctypes.byref(la), stream())
         torch.cuda.synchronize()
         return rc, a, c, d
@@ -168,9 +170,12 @@ def ppo_case(lib, rows, A, clipped):
     return (o_actor, o_critic, d_ref), fused_run
 
 
-@pytest.mark.parametrize("clipped", [1, 0])
-@pytest.mark.parametrize("A", [12, 5])
-@pytest.mark.parametrize("rows", [1, 64, 65, 257, 8259])
+# A = 1, 4 and 9: the AMAX = 4 instantiation, its 16-byte gathers (A = 4), and a head that is no multiple of 4 in the AMAX = 12 one
+PPO_CASES = [(rows, A, clipped) for clipped in (1, 0) for A in (12, 5) for rows in (1, 64, 65, 257, 8259)] + \
+            [(rows, A, clipped) for clipped in (1, 0) for A in (1, 4, 9) for rows in (65, 257)]
+
+
+@pytest.mark.parametrize("rows,A,clipped", PPO_CASES)
 def test_ppo_tail_equals_three_launches(lib, rows, A, clipped):
     (o_actor, o_critic, d_ref), fused_run = ppo_case(lib, rows, A, clipped)
     assert all(bool(torch.isfinite(t).all()) for t in d_ref)
@@ -203,13 +208,15 @@ def num_train_cases(rows):
 
 
 MSE_CASES = [(rows, n) for rows in (2, 64, 65, 257, 8259, 16449) for n in num_train_cases(rows)]
+# npv = 2 as the policy has it; then widths whose targets pass the 8 gathered ahead and whose head columns reach the second 16-byte chunk
+MSE_PARAMS = [pytest.param(rows, n, selective, 2, id=f"{rows}-{n}-{selective}") for selective in (0, 1) for rows, n in MSE_CASES] + \
+             [pytest.param(rows, n, selective, npv, id=f"{rows}-{n}-{selective}-npv{npv}") for selective in (0, 1) for npv in (1, 7, 9, 13, 64)
+              for rows in (65, 257) for n in num_train_cases(rows)[1:]]
 
 
-@pytest.mark.parametrize("selective", [0, 1])
-@pytest.mark.parametrize("rows,num_train", MSE_CASES)
-def test_mse_tail_equals_three_launches(lib, rows, num_train, selective):
+@pytest.mark.parametrize("rows,num_train,selective,npv", MSE_PARAMS)
+def test_mse_tail_equals_three_launches(lib, rows, num_train, selective, npv):
     from go1_gym_learn.ppo_cse import fused as F
-    npv = 2
     g = gen(7 * rows + num_train + selective)
     net = Net(rows, g)
     S = 2 * rows + 3

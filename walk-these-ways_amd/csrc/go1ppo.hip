@@ -438,7 +438,7 @@ __global__ __launch_bounds__(256) void loss_kernel(Go1PpoLossArgs a) {
 #pragma unroll 16
     for (unsigned b = 0; b < gridDim.x; b++) t += det_loss_slab[(int64_t)b * DET_LOSS_W + c];
     float* dst = c < 4 ? (c == 0 ? a.surrogate_loss : c == 1 ? a.value_loss : c == 2 ? a.kl : a.d_value_bias)
-                       : c < 4 + A ? a.d_std + (c - 4) : a.d_mean_bias + (c - 4 - A);
+                       : c < 4 + A ? (a.d_std ? a.d_std + (c - 4) : nullptr) : (a.d_mean_bias ? a.d_mean_bias + (c - 4 - A) : nullptr);
     if (!dst) continue;
     float s = *dst + t;
     // entropy term: loss -= entropy_coef * (sum log sigma + const)  ->  d/d sigma_j = -entropy_coef / sigma_j  (once)
@@ -494,7 +494,7 @@ __global__ __launch_bounds__(256) void mse_kernel(const bf16_t* pred, int pred_l
     float t = 0.f;
 #pragma unroll 16
     for (unsigned b = 0; b < gridDim.x; b++) t += det_mse_slab[(int64_t)b * DET_MSE_W + c];
-    float* dst = c < ncol ? d_pred_bias + c : c == ncol ? train_loss : test_loss;
+    float* dst = c < ncol ? (d_pred_bias ? d_pred_bias + c : nullptr) : c == ncol ? train_loss : test_loss;
     if (dst) *dst += t;
   }
 }
@@ -1155,6 +1155,10 @@ extern "C" int go1ppo_elu_bwd(const void* d, int ld_d, const void* h, int ld_h, 
 extern "C" int go1ppo_loss(const Go1PpoLossArgs* a, void* stream) {
   if (!a || a->rows <= 0 || a->num_actions <= 0 || a->num_actions > GO1PPO_MAX_ACTIONS || a->head_ld < a->num_actions) return -1;
   if ((a->rows + 255) / 256 > DET_MAX_BLOCKS) return -1;                 // one row of det_loss_slab per workgroup
+  // inputs and the per-sample gradients are required (the old values only where the clipped value loss reads them); the sums are optional
+  if (!a->mean || !a->value || !a->std || !a->idx || !a->actions || !a->old_mu || !a->old_sigma || !a->old_logp || !a->advantages ||
+      !a->returns || !a->d_mean || !a->d_value || (a->use_clipped_value_loss && !a->old_values))
+    return -1;
   // (measured: 64-thread workgroups — 384 instead of 96 — are slower, 33 vs 26 us: four times the atomics on the same 28 words)
   // (one wavefront per workgroup — 384 workgroups instead of 96 — measured 32 us against 22: four times the same-address atomics of the reductions)
   // (measured, round 6 — profiles/r06_loss_kernel_ablation.txt: the same-address atomics are 1 us of the kernel's 16-22; meeting the sums through
@@ -1168,7 +1172,7 @@ extern "C" int go1ppo_loss(const Go1PpoLossArgs* a, void* stream) {
 extern "C" int go1ppo_mse(const void* pred, int pred_ld, const float* target, int npv, const int64_t* idx, int64_t rows,
                           int64_t num_train, int selective, void* d_pred, float* d_pred_bias, float* train_loss,
                           float* test_loss, void* stream) {
-  if (!pred || !target || !idx || rows <= 0 || num_train <= 0 || num_train >= rows || npv <= 0 || npv > pred_ld) return -1;
+  if (!pred || !target || !idx || !d_pred || !train_loss || !test_loss || rows <= 0 || num_train <= 0 || num_train >= rows || npv <= 0 || npv > pred_ld) return -1;
   if (npv > GO1PPO_HEAD || (rows + 255) / 256 > DET_MAX_BLOCKS) return -1;   // one row of det_mse_slab (npv + 2 columns) per workgroup
   mse_kernel<<<dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(
       (const bf16_t*)pred, pred_ld, target, npv, idx, rows, num_train, selective, (bf16_t*)d_pred, d_pred_bias, train_loss, test_loss);

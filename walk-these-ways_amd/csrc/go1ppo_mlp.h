@@ -748,7 +748,7 @@ __device__ __forceinline__ void mlp2_tail_body(const Go1PpoMlp2Tail& N, const Go
       const int j = c < 4 ? 0 : (c - 4) % TAIL_AMAX;
       if (c >= 4 && j >= A) return;
       float* dst = c < 4 ? (c == 0 ? a.surrogate_loss : c == 1 ? a.value_loss : c == 2 ? a.kl : a.d_value_bias)
-                         : c < 4 + TAIL_AMAX ? a.d_std + j : a.d_mean_bias + j;
+                         : c < 4 + TAIL_AMAX ? (a.d_std ? a.d_std + j : nullptr) : (a.d_mean_bias ? a.d_mean_bias + j : nullptr);
       if (!dst) return;
       float sres = *dst + tsum;
       // entropy term: loss -= entropy_coef * (sum log sigma + const)  ->  d/d sigma_j = -entropy_coef / sigma_j  (once)
