@@ -44,6 +44,13 @@ With `--joints` the velocity grid is swept with the per-joint table armed beside
 torque, speed, acceleration, driving and braking power, soft-limit excess and the shares of steps at the torque clip and at the
 URDF's speed limit for each of the twelve joints, and a torque-speed histogram per joint.  `<out>/eval/<preset>_joints.json` and the
 torque-speed envelope `<preset>_envelope.png` are written and the per-joint table is printed and appended to `<preset>_joints.md`.
+
+    python tools/eval_sweep.py --checkpoint RUN_DIR/checkpoints --out RUN_DIR --feet --vx 0.5 1.0 1.5
+
+With `--feet` the velocity grid is swept with the foot-loading table armed beside the scalar one (go1_gym_learn.eval_metrics.feet,
+include/go1feet.h): duty factor, vertical force, friction use, touchdown speed, impulse and slip per stance for each of the four feet,
+and the ground-reaction-force profile over the gait phase.  `<out>/eval/<preset>_feet.json` and the profile figure `<preset>_grf.png`
+are written and the per-foot table is printed and appended to `<preset>_feet.md`.
 Run on the GPU box."""
 import argparse
 import json
@@ -131,6 +138,7 @@ def parse_args(argv=None):
     ap.add_argument("--direction", nargs="+", type=float, default=None,
                     help="with --push: directions in degrees in the robot's heading frame (0 a shove from behind, 90 a push to the left)")
     ap.add_argument("--joints", action="store_true", help="measure per-joint actuator usage over the velocity grid, beside the scalar table")
+    ap.add_argument("--feet", action="store_true", help="measure per-foot ground reaction forces over the velocity grid, beside the scalar table")
     ap.add_argument("--out", required=True)
     a = ap.parse_args(argv)
     a.tiles = a.terrain == "tiles"
@@ -150,6 +158,8 @@ def parse_args(argv=None):
     a.vx = a.vx or [0.5, 1.0, 1.5]
     if a.joints and (a.tiles or a.response or a.behaviour or a.push):
         ap.error("--joints excludes --terrain (bare), --response, --behaviour and --push")
+    if a.feet and (a.tiles or a.response or a.behaviour or a.push or a.joints):
+        ap.error("--feet excludes --terrain (bare), --response, --behaviour, --push and --joints")
     if a.switch and not a.response:
         ap.error("--switch needs --response")
     if a.trace_envs and not (a.response or a.push):
@@ -246,6 +256,20 @@ def run_joints(a, policy, grid):
                              soft_torque_limit=res["soft_torque_limit"], soft_vel_limit=res["soft_vel_limit"])
 
 
+def run_feet(a, policy, grid):
+    from go1_gym_learn.eval_metrics import feet
+    for preset in a.presets:
+        res = feet.run_foot_sweep(policy, preset, grid, num_envs=a.envs, steps=a.steps, warmup_steps=a.warmup_steps, seed=a.seed, terrain=a.terrain)
+        stem = os.path.join(a.out, "eval", preset)
+        with open(stem + "_feet.json", "w") as f:
+            json.dump(feet.foot_to_json(res), f, indent=1)
+        text = f"### {preset}: {a.envs} environments, {a.steps} steps, vx {a.vx}, foot loading\n\n" + feet.foot_markdown_table(res) + "\n"
+        print(text)
+        with open(stem + "_feet.md", "a") as f:
+            f.write(text + "\n")
+        feet.plot_grf(res, stem + "_grf.png")
+
+
 def behaviour_axes(a):
     """{command name: [values]} of the --axis options, in the order given"""
     from go1_gym_learn.eval_metrics.behaviour import COMMAND_INDEX
@@ -274,6 +298,8 @@ def main(argv=None):
         return run_terrain(a, policy)
     if a.joints:
         return run_joints(a, policy, grid)
+    if a.feet:
+        return run_feet(a, policy, grid)
     if a.behaviour:
         from go1_gym_learn.eval_metrics import behaviour
         axes = behaviour_axes(a)

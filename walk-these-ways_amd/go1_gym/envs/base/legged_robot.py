@@ -153,6 +153,7 @@ class LeggedRobot(BaseTask):
         self._push = None                 # go1eval_host.Go1Push, created by the first push_robots()
         self._traversal = None            # go1eval_host.Go1Terrain, created by the first start_terrain_metrics()
         self._joints = None               # go1eval_host.Go1Joints, created by the first start_joint_metrics()
+        self._feet = None                 # go1feet_host.Go1Feet, created by the first start_foot_metrics()
         if eval_cfg is not None:          # reference legged_robot.py:41-42
             self._parse_cfg(eval_cfg)
         self._parse_cfg(cfg)
@@ -453,6 +454,8 @@ class LeggedRobot(BaseTask):
             self._traversal.accumulate()
         if self._joints is not None and self._joints.armed:
             self._joints.accumulate()
+        if self._feet is not None and self._feet.armed:
+            self._feet.accumulate()
         if self._curriculum_sync and (self.common_step_counter + 1) % self.sim_config.curriculum_update_interval == 0:
             # ONE exchange for the last `curriculum_update_interval` steps' success counts (a slot per step), then the per-step
             # updates in order: every rank applies what a single process over the concatenated shards would
@@ -752,6 +755,29 @@ class LeggedRobot(BaseTask):
         (groups, 12, 8, 8) torque-bin x speed-bin counts, "tau_edges", "vel_edges": (12, 9), and the per-environment "steps", "resets",
         "prev_dof_vel", "env_hist"}: one reduction launch and the device-to-host copies"""
         return self._started("read_joint_metrics", "_joints", "start_joint_metrics").read()
+
+    # ---- foot loading (include/go1feet.h, libgo1feet.so: a library of its own): twelve values per foot (contact, vertical and horizontal
+    # force, friction use, force excess, impact speed, and per stance peak force, impulse, slip and time) and the GRF profile over the
+    # gait phase.  One more launch per step while it is armed, after the joint family's; independent of the other measurements.
+    def start_foot_metrics(self, groups, warmup_steps=0):
+        """begin a foot-loading measurement: `groups` = one int per environment (the row of the result tables it counts towards, -1 = not
+        evaluated); steps with episode_length_buf <= warmup_steps fold nothing and break every stance.  The ground's friction and
+        max_contact_force are the simulator's (terrain.static_friction, rewards.max_contact_force)"""
+        self._need_gpu_metrics("start_foot_metrics")
+        if self._feet is None:
+            import go1feet_host
+            self._feet = go1feet_host.Go1Feet(self.sim_config, self.buffers, self.dt)
+        self._feet.arm(groups, warmup_steps)
+
+    def stop_foot_metrics(self):
+        """stop folding steps; what was measured stays readable"""
+        self._disarm("stop_foot_metrics", "_feet")
+
+    def read_foot_metrics(self):
+        """go1feet_host.Go1Feet.read(): {"metrics": {name: (groups, 4, 6)}, "groups": (groups, 3) array of envs, steps, resets, "profile":
+        (groups, 4, 16) mean vertical force per phase bin, "profile_sum", "profile_count", "phase_edges": (17,), and the per-environment
+        state}: one reduction launch and the device-to-host copies"""
+        return self._started("read_foot_metrics", "_feet", "start_foot_metrics").read()
 
     def render(self, mode="rgb_array"):
         """reference :1612-1620: env 0 from its recording camera, now: (240, 360, 4) uint8 RGBA"""
