@@ -51,6 +51,14 @@ With `--feet` the velocity grid is swept with the foot-loading table armed besid
 include/go1feet.h): duty factor, vertical force, friction use, touchdown speed, impulse and slip per stance for each of the four feet,
 and the ground-reaction-force profile over the gait phase.  `<out>/eval/<preset>_feet.json` and the profile figure `<preset>_grf.png`
 are written and the per-foot table is printed and appended to `<preset>_feet.md`.
+
+    python tools/eval_sweep.py --checkpoint RUN_DIR/checkpoints --out RUN_DIR --trunk --vx 0.5 1.0 1.5 --segment-steps 50 --tilt-limit 0.25
+
+With `--trunk` the velocity grid is swept with the trunk table armed beside the scalar one (go1_gym_learn.eval_metrics.trunk,
+include/go1trunk.h): roll, pitch and tilt, their rates, the trunk's accelerations, the number of supporting feet, the base's margin inside
+the support polygon, and the lateral drift, heading drift and progress error per straight segment of `--segment-steps` steps;
+`--tilt-limit` is the sine beyond which a step counts as tilted too far.  `<out>/eval/<preset>_trunk.json` and the tilt histogram
+`<preset>_tilt.png` are written and the table is printed and appended to `<preset>_trunk.md`.
 Run on the GPU box."""
 import argparse
 import json
@@ -139,6 +147,9 @@ def parse_args(argv=None):
                     help="with --push: directions in degrees in the robot's heading frame (0 a shove from behind, 90 a push to the left)")
     ap.add_argument("--joints", action="store_true", help="measure per-joint actuator usage over the velocity grid, beside the scalar table")
     ap.add_argument("--feet", action="store_true", help="measure per-foot ground reaction forces over the velocity grid, beside the scalar table")
+    ap.add_argument("--trunk", action="store_true", help="measure trunk motion, support margin and path drift over the velocity grid, beside the scalar table")
+    ap.add_argument("--segment-steps", type=int, default=None, help="with --trunk: policy steps of a drift segment, default 50")
+    ap.add_argument("--tilt-limit", type=float, default=None, help="with --trunk: the sine of the tilt beyond which a step is counted, default 0.25")
     ap.add_argument("--out", required=True)
     a = ap.parse_args(argv)
     a.tiles = a.terrain == "tiles"
@@ -160,6 +171,15 @@ def parse_args(argv=None):
         ap.error("--joints excludes --terrain (bare), --response, --behaviour and --push")
     if a.feet and (a.tiles or a.response or a.behaviour or a.push or a.joints):
         ap.error("--feet excludes --terrain (bare), --response, --behaviour, --push and --joints")
+    if a.trunk and (a.tiles or a.response or a.behaviour or a.push or a.joints or a.feet):
+        ap.error("--trunk excludes --terrain (bare), --response, --behaviour, --push, --joints and --feet")
+    if not a.trunk and (a.segment_steps is not None or a.tilt_limit is not None):
+        ap.error("--segment-steps and --tilt-limit need --trunk")
+    if a.trunk:
+        a.segment_steps = 50 if a.segment_steps is None else a.segment_steps
+        a.tilt_limit = 0.25 if a.tilt_limit is None else a.tilt_limit
+        if a.segment_steps < 1 or not 0.0 <= a.tilt_limit < float("inf"):
+            ap.error("--segment-steps has to be at least 1 and --tilt-limit a finite sine that is not negative")
     if a.switch and not a.response:
         ap.error("--switch needs --response")
     if a.trace_envs and not (a.response or a.push):
@@ -270,6 +290,21 @@ def run_feet(a, policy, grid):
         feet.plot_grf(res, stem + "_grf.png")
 
 
+def run_trunk(a, policy, grid):
+    from go1_gym_learn.eval_metrics import trunk
+    for preset in a.presets:
+        res = trunk.run_trunk_sweep(policy, preset, grid, num_envs=a.envs, steps=a.steps, warmup_steps=a.warmup_steps, seed=a.seed, terrain=a.terrain,
+                                    segment_steps=a.segment_steps, tilt_limit=a.tilt_limit)
+        stem = os.path.join(a.out, "eval", preset)
+        with open(stem + "_trunk.json", "w") as f:
+            json.dump(trunk.trunk_to_json(res), f, indent=1)
+        text = f"### {preset}: {a.envs} environments, {a.steps} steps, vx {a.vx}, trunk motion\n\n" + trunk.trunk_markdown_table(res) + "\n"
+        print(text)
+        with open(stem + "_trunk.md", "a") as f:
+            f.write(text + "\n")
+        trunk.plot_tilt(res, stem + "_tilt.png")
+
+
 def behaviour_axes(a):
     """{command name: [values]} of the --axis options, in the order given"""
     from go1_gym_learn.eval_metrics.behaviour import COMMAND_INDEX
@@ -300,6 +335,8 @@ def main(argv=None):
         return run_joints(a, policy, grid)
     if a.feet:
         return run_feet(a, policy, grid)
+    if a.trunk:
+        return run_trunk(a, policy, grid)
     if a.behaviour:
         from go1_gym_learn.eval_metrics import behaviour
         axes = behaviour_axes(a)

@@ -154,6 +154,7 @@ class LeggedRobot(BaseTask):
         self._traversal = None            # go1eval_host.Go1Terrain, created by the first start_terrain_metrics()
         self._joints = None               # go1eval_host.Go1Joints, created by the first start_joint_metrics()
         self._feet = None                 # go1feet_host.Go1Feet, created by the first start_foot_metrics()
+        self._trunk = None                # go1trunk_host.Go1Trunk, created by the first start_trunk_metrics()
         if eval_cfg is not None:          # reference legged_robot.py:41-42
             self._parse_cfg(eval_cfg)
         self._parse_cfg(cfg)
@@ -456,6 +457,8 @@ class LeggedRobot(BaseTask):
             self._joints.accumulate()
         if self._feet is not None and self._feet.armed:
             self._feet.accumulate()
+        if self._trunk is not None and self._trunk.armed:
+            self._trunk.accumulate()
         if self._curriculum_sync and (self.common_step_counter + 1) % self.sim_config.curriculum_update_interval == 0:
             # ONE exchange for the last `curriculum_update_interval` steps' success counts (a slot per step), then the per-step
             # updates in order: every rank applies what a single process over the concatenated shards would
@@ -778,6 +781,32 @@ class LeggedRobot(BaseTask):
         (groups, 4, 16) mean vertical force per phase bin, "profile_sum", "profile_count", "phase_edges": (17,), and the per-environment
         state}: one reduction launch and the device-to-host copies"""
         return self._started("read_foot_metrics", "_feet", "start_foot_metrics").read()
+
+    # ---- trunk motion (include/go1trunk.h, libgo1trunk.so: a library of its own): seventeen values per environment (roll, pitch and tilt
+    # as sines, their rates, the vertical velocity, the trunk's accelerations, the number of supporting feet, the base's margin inside the
+    # support polygon, and per straight segment the lateral drift, the heading drift and the progress error) and a tilt histogram.  One
+    # more launch per step while it is armed, after the foot family's; independent of the other measurements.
+    def start_trunk_metrics(self, groups, warmup_steps=0, segment_steps=50, tilt_limit=0.25):
+        """begin a trunk measurement: `groups` = one int per environment (the row of the result tables it counts towards, -1 = not
+        evaluated); steps with episode_length_buf <= warmup_steps fold nothing and end an open segment.  segment_steps: the policy steps
+        of a drift segment; 50 is 1 s, two strides or more at 2 Hz and above, so the sway within a stride cancels.  tilt_limit: the sine
+        beyond which a step counts as tilt_exceeded; 0.25 (about 14.5 degrees) is a placeholder, as the push family's band is: no
+        measurement of a robot's falls stands behind it"""
+        self._need_gpu_metrics("start_trunk_metrics")
+        if self._trunk is None:
+            import go1trunk_host
+            self._trunk = go1trunk_host.Go1Trunk(self.sim_config, self.buffers, self.dt)
+        self._trunk.arm(groups, warmup_steps, segment_steps=segment_steps, tilt_limit=tilt_limit)
+
+    def stop_trunk_metrics(self):
+        """stop folding steps; what was measured stays readable"""
+        self._disarm("stop_trunk_metrics", "_trunk")
+
+    def read_trunk_metrics(self):
+        """go1trunk_host.Go1Trunk.read(): {"metrics": {name: (groups, 6)}, "groups": (groups, 4) array of envs, steps, resets,
+        segments_dropped, "tilt_hist": (groups, 16), "tilt_edges": (17,), the per-environment state and "env_max_tilt"}: one reduction
+        launch and the device-to-host copies"""
+        return self._started("read_trunk_metrics", "_trunk", "start_trunk_metrics").read()
 
     def render(self, mode="rgb_array"):
         """reference :1612-1620: env 0 from its recording camera, now: (240, 360, 4) uint8 RGBA"""
