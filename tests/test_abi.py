@@ -35,6 +35,21 @@ def test_library_exports_every_declared_symbol():
     assert g.library_stamp(H.LIB_PATH) == want and want.encode() in lib.go1sim_version()
 
 
+@pytest.mark.parametrize("name", ["sim", "ppo", "render", "eval", "feet", "trunk"])
+def test_source_lists_are_what_the_compiler_reads(name):
+    """a library's *_sources() is exactly the set of files of the tree its translation unit reads, as the compiler itself lists them
+    (-MM: the main file and every header outside the system's directories): a header that is included but missing from the list, whose
+    edits would leave the stamp unchanged, cannot ship, and neither can a listed file that nothing includes"""
+    import subprocess
+    import __graft_entry__ as g
+    sources, flags = getattr(g, name + "_sources")(), getattr(g, name.upper() + "_FLAGS")
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    out = subprocess.run([hipcc] + flags + ["--cuda-host-only", "-MM", sources[0]], cwd=g.CSRC, check=True, capture_output=True, text=True).stdout
+    read = [os.path.normpath(os.path.join(g.CSRC, f)) for f in out.split(":", 1)[1].replace("\\\n", " ").split()]
+    read = {f for f in read if not f.startswith("/opt/")}
+    assert read == {os.path.normpath(f) for f in sources} and len(read) == len(sources), (sorted(read), sources)
+
+
 def test_build_rebuilds_a_library_whose_stamp_does_not_match_the_sources(tmp_path, monkeypatch):
     """build_ppo_hip() calls the compiler for a library built from other sources (here: a copy of the shipped one with its stamp overwritten)
     and does not for one whose stamp matches; the stamp reader refuses an absent, an unstamped and an ambiguous file"""

@@ -6,7 +6,6 @@ import ctypes
 import json
 import os
 import re
-import subprocess
 import sys
 import types
 
@@ -16,6 +15,7 @@ import torch
 
 import behaviour_ref as R
 import eval_ref as E
+from test_eval_metrics import eval_emu
 
 REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 HEADER = os.path.join(REPO, "include", "go1eval.h")
@@ -247,25 +247,6 @@ def test_two_feet_touching_down_in_one_step_fold_in_foot_order():
 
 
 # ---- 4. the kernel source under the SIMT emulator against the model -----------------------------------------------------------------------
-def _build_behaviour_emu():
-    """go1eval.hip, unmodified, compiled for the host against tests/emu's stand-in hip/hip_runtime.h and its fiber scheduler"""
-    import __graft_entry__ as g
-    emu = os.path.join(REPO, "tests", "emu")
-    src = os.path.join(REPO, "walk-these-ways_amd", "csrc", "go1eval.hip")
-    runtime = os.path.join(emu, "emu_runtime.cpp")
-    flags = ["-x", "c++", "-std=c++17", "-O1", "-g", "-fPIC", "-shared", "-fopenmp", "-ffp-contract=off", "-Wno-everything"]
-    out = os.path.join(emu, "_build", "libgo1eval_behaviour_emu.so")
-    want = g.source_hash([src, HEADER, os.path.join(emu, "hip", "hip_runtime.h"), runtime], flags)
-    stamp = out + ".stamp"
-    if not (os.path.exists(out) and os.path.exists(stamp) and open(stamp).read().strip() == want):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        compiler = os.environ.get("EMU_CXX", "/opt/rocm/lib/llvm/bin/clang++")
-        subprocess.check_call([compiler] + flags + ["-I", emu, "-o", out, src, runtime], cwd=os.path.dirname(src))
-        with open(stamp, "w") as fh:
-            fh.write(want)
-    return out
-
-
 class Synthetic:
     """snapshots whose contacts follow per-foot periodic schedules (period 3..6 steps, random phase, occasional chatter)"""
 
@@ -309,7 +290,7 @@ class Synthetic:
 @pytest.mark.parametrize("N,P,num_commands", [(300, 17, 15), (64, 0, 12)])
 def test_emulated_behaviour_kernels_follow_the_model(N, P, num_commands):
     import go1eval_host as G
-    lib = ctypes.CDLL(_build_behaviour_emu())
+    lib = ctypes.CDLL(eval_emu())
     rng = np.random.default_rng(17 + N)
     W, groups, target = 2, 3, 0.30
     group = rng.integers(-1, groups + 1, N).astype(np.int32)           # includes -1 and an id outside the table

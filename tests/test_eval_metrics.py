@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import eval_ref as E
+from util import build_emu
 
 REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 HEADER = os.path.join(REPO, "include", "go1eval.h")
@@ -58,8 +59,8 @@ def test_eval_library_exports_what_the_header_declares_with_the_source_stamp():
 def test_eval_library_is_separate_from_the_other_libraries():
     import __graft_entry__ as g
     names = {os.path.basename(f) for f in g.sim_sources() + g.ppo_sources() + g.render_sources()}
-    assert not names & {"go1eval.hip", "go1eval.h"}
-    assert {os.path.basename(f) for f in g.eval_sources()} == {"go1eval.hip", "go1eval.h"}
+    assert not names & {"go1eval.hip", "go1eval.h", "go1_tables.h"}
+    assert {os.path.basename(f) for f in g.eval_sources()} == {"go1eval.hip", "go1eval.h", "go1_tables.h"}
 
 
 def test_missing_eval_library_fails_loudly(tmp_path):
@@ -285,23 +286,10 @@ def test_model_metric_values_by_hand():
 
 
 # ---- the kernel source under the SIMT emulator against the model ---------------------------------------------------------------------
-def _build_eval_emu():
-    """tests/emu compiles the product's device code for the host (tests/emu/build.py does this for go1sim.hip): the same for
-    go1eval.hip, unmodified, against the stand-in hip/hip_runtime.h and the fiber scheduler"""
+def eval_emu():
+    """go1eval.hip under the SIMT emulator (util.build_emu): the one emulator library of every family of libgo1eval"""
     import __graft_entry__ as g
-    emu = os.path.join(REPO, "tests", "emu")
-    src = os.path.join(REPO, "walk-these-ways_amd", "csrc", "go1eval.hip")
-    deps = [src, HEADER, os.path.join(emu, "hip", "hip_runtime.h"), os.path.join(emu, "emu_runtime.cpp")]
-    flags = ["-x", "c++", "-std=c++17", "-O1", "-g", "-fPIC", "-shared", "-fopenmp", "-ffp-contract=off", "-Wno-everything"]
-    out = os.path.join(emu, "_build", "libgo1eval_emu.so")
-    want = g.source_hash(deps, flags)
-    if not (os.path.exists(out) and os.path.exists(out + ".stamp") and open(out + ".stamp").read().strip() == want):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        clang = os.environ.get("EMU_CXX", "/opt/rocm/lib/llvm/bin/clang++")
-        subprocess.check_call([clang] + flags + ["-I", emu, "-o", out, src, os.path.join(emu, "emu_runtime.cpp")], cwd=os.path.dirname(src))
-        with open(out + ".stamp", "w") as fh:
-            fh.write(want)
-    return out
+    return build_emu(g.eval_sources(), "libgo1eval_emu.so")
 
 
 def random_snapshot(rng, N, P, step):
@@ -319,7 +307,7 @@ def random_snapshot(rng, N, P, step):
 @pytest.mark.parametrize("N,P", [(300, 17), (64, 0)])
 def test_emulated_kernels_follow_the_model(N, P):
     import go1eval_host as G
-    lib = ctypes.CDLL(_build_eval_emu())
+    lib = ctypes.CDLL(eval_emu())
     rng = np.random.default_rng(5 + N)
     W, groups = 2, 3
     group = rng.integers(-1, groups + 1, N).astype(np.int32)           # includes -1 and an id outside the table

@@ -19,9 +19,11 @@ import torch
 import feet_ref as F
 from test_eval_return_codes import Call, cfg, each, nobody, null
 from test_response_trace import C_TYPES, REPO, bits, enum_order, struct_fields
+from util import build_emu
 
 HEADER = os.path.join(REPO, "include", "go1feet.h")
 SOURCE = os.path.join(REPO, "walk-these-ways_amd", "csrc", "go1feet.hip")
+TABLES = os.path.join(REPO, "walk-these-ways_amd", "csrc", "go1_tables.h")
 NAN, INF = float("nan"), float("inf")
 f32 = np.float32
 ACCUMULATORS = ["count", "sum", "sumsq", "min", "max", "nonfinite"]
@@ -71,11 +73,15 @@ def test_exported_symbols_are_the_headers_declarations():
 
 def test_sources_flags_and_stamp():
     import __graft_entry__ as g
-    assert g.feet_sources() == [SOURCE, HEADER] and g.FEET_FLAGS == g.EVAL_FLAGS and "-ffp-contract=off" in g.FEET_FLAGS
-    assert g.eval_sources() == [os.path.join(REPO, "walk-these-ways_amd", "csrc", "go1eval.hip"), os.path.join(REPO, "include", "go1eval.h")]
-    for others in (g.sim_sources(), g.ppo_sources(), g.render_sources(), g.eval_sources()):
+    assert g.feet_sources() == [SOURCE, TABLES, HEADER] and g.FEET_FLAGS == g.EVAL_FLAGS and "-ffp-contract=off" in g.FEET_FLAGS
+    assert g.eval_sources() == [os.path.join(REPO, "walk-these-ways_amd", "csrc", "go1eval.hip"), TABLES, os.path.join(REPO, "include", "go1eval.h")]
+    for others in (g.sim_sources(), g.ppo_sources(), g.render_sources()):
         assert not set(others) & set(g.feet_sources())
-    assert "go1eval" not in re.sub(r"//.*", "", open(SOURCE).read())          # the library shares no source with libgo1eval
+    for others in (g.eval_sources(), g.trunk_sources()):                      # the metric libraries share one header, and nothing else
+        assert set(others) & set(g.feet_sources()) == {TABLES}
+    assert "go1eval" not in re.sub(r"//.*", "", open(SOURCE).read())          # the library names nothing of libgo1eval ...
+    shared = re.sub(r"//.*", "", open(TABLES).read())                         # ... and the shared header names no library
+    assert "go1eval" not in shared and "go1feet" not in shared and "go1trunk" not in shared
     out = g.build_feet_hip()
     assert os.path.basename(out) == "libgo1feet.so" and g.library_stamp(out) == g.source_hash(g.feet_sources(), g.FEET_FLAGS)
     lib = ctypes.CDLL(out)                                                   # dlopen needs no GPU
@@ -310,28 +316,11 @@ def test_model_phase_bins():
 
 
 # ---- 5. go1feet.hip under the SIMT emulator against the model ---------------------------------------------------------------------------------
-def _build_feet_emu():
-    """tests/emu compiles the product's device code for the host, as test_eval_metrics._build_eval_emu does for go1eval.hip: the same
-    for go1feet.hip, unmodified, under its own output name"""
-    import __graft_entry__ as g
-    emu = os.path.join(REPO, "tests", "emu")
-    deps = [SOURCE, HEADER, os.path.join(emu, "hip", "hip_runtime.h"), os.path.join(emu, "emu_runtime.cpp")]
-    flags = ["-x", "c++", "-std=c++17", "-O1", "-g", "-fPIC", "-shared", "-fopenmp", "-ffp-contract=off", "-Wno-everything"]
-    out = os.path.join(emu, "_build", "libgo1feet_emu.so")
-    want = g.source_hash(deps, flags)
-    if not (os.path.exists(out) and os.path.exists(out + ".stamp") and open(out + ".stamp").read().strip() == want):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        clang = os.environ.get("EMU_CXX", "/opt/rocm/lib/llvm/bin/clang++")
-        subprocess.check_call([clang] + flags + ["-I", emu, "-o", out, SOURCE, os.path.join(emu, "emu_runtime.cpp")], cwd=os.path.dirname(SOURCE))
-        with open(out + ".stamp", "w") as fh:
-            fh.write(want)
-    return out
-
-
 @pytest.fixture(scope="module")
 def emu():
+    import __graft_entry__ as g
     import go1feet_host as G
-    return G.load_library(_build_feet_emu())
+    return G.load_library(build_emu(g.feet_sources(), "libgo1feet_emu.so"))
 
 
 def feet_on(device, cfg_, N, lib=None):

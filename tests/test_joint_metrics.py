@@ -13,7 +13,7 @@ import pytest
 import torch
 
 import joint_ref as J
-from test_response_trace import C_TYPES, HEADER, REPO, _build_eval_emu, bits, enum_order, struct_fields
+from test_response_trace import C_TYPES, HEADER, REPO, eval_emu, bits, enum_order, struct_fields
 from test_terrain_metrics import scripted_groups
 
 NAN = float("nan")
@@ -254,7 +254,7 @@ def test_model_previous_velocity_across_a_reset_and_the_warm_up():
 @pytest.fixture(scope="module")
 def emu():
     import go1eval_host as G
-    return G.load_library(_build_eval_emu())
+    return G.load_library(eval_emu())
 
 
 def joints_on(device, cfg, N, lib=None):

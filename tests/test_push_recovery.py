@@ -14,7 +14,7 @@ import pytest
 import torch
 
 import recovery_ref as P
-from test_response_trace import C_TYPES, HEADER, REPO, _build_eval_emu, bits, enum_order, struct_fields
+from test_response_trace import C_TYPES, HEADER, REPO, eval_emu, bits, enum_order, struct_fields
 
 NAN = float("nan")
 f32 = np.float32
@@ -258,7 +258,7 @@ def test_model_group_table():
 @pytest.fixture(scope="module")
 def emu():
     import go1eval_host as G
-    return G.load_library(_build_eval_emu())
+    return G.load_library(eval_emu())
 
 
 def unit_quaternions(rng, n):

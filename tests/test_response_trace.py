@@ -11,7 +11,7 @@ import pytest
 import torch
 
 import response_ref as P
-from test_eval_metrics import _build_eval_emu
+from test_eval_metrics import eval_emu
 
 REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 HEADER = os.path.join(REPO, "include", "go1eval.h")
@@ -261,7 +261,7 @@ def test_model_group_table():
 @pytest.fixture(scope="module")
 def emu():
     import go1eval_host as G
-    lib = ctypes.CDLL(_build_eval_emu())
+    lib = ctypes.CDLL(eval_emu())
     lib.go1eval_trace_record.argtypes = [ctypes.POINTER(G.Go1TraceConfig), ctypes.POINTER(G.Go1TraceBuffers), ctypes.c_int32, ctypes.c_void_p]
     return lib
 
@@ -423,7 +423,7 @@ def test_go1trace_through_the_emulated_library():
     rows, and response() (one packed output buffer, one copy) against the model's values, statuses and table"""
     import types
     import go1eval_host as G
-    lib = G.load_library(_build_eval_emu())
+    lib = G.load_library(eval_emu())
     rng = np.random.default_rng(9)
     N, points, ids = 70, 5, [69, 0, 33]
     first = random_snapshot(rng, N, points)

@@ -12,7 +12,7 @@ import pytest
 import torch
 
 import terrain_ref as T
-from test_response_trace import C_TYPES, HEADER, REPO, _build_eval_emu, bits, enum_order, struct_fields
+from test_response_trace import C_TYPES, HEADER, REPO, eval_emu, bits, enum_order, struct_fields
 
 NAN = float("nan")
 f32 = np.float32
@@ -250,7 +250,7 @@ def test_model_warmup_swing_stumble_and_collision():
 @pytest.fixture(scope="module")
 def emu():
     import go1eval_host as G
-    return G.load_library(_build_eval_emu())
+    return G.load_library(eval_emu())
 
 
 def terrain_on(device, geo, N, lib=None):

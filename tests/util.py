@@ -12,6 +12,27 @@ from golden.variants import apply_variant
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 
 
+def build_emu(sources, name, defines=()):
+    """tests/emu compiles the product's device code for the host (tests/emu/build.py does this for go1sim.hip): sources[0], a library's
+    .hip, unmodified, against the stand-in hip/hip_runtime.h and the fiber scheduler -> tests/emu/_build/<name>.  `sources` is the
+    library's __graft_entry__.*_sources(): the stamp beside the output covers all of it and the two emulator files, so an edit to a
+    shared header rebuilds every emulator library that includes it."""
+    import subprocess
+    import __graft_entry__ as g
+    emu = os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu")
+    runtime = os.path.join(emu, "emu_runtime.cpp")
+    flags = ["-x", "c++", "-std=c++17", "-O1", "-g", "-fPIC", "-shared", "-fopenmp", "-ffp-contract=off", "-Wno-everything"] + ["-D" + d for d in defines]
+    out = os.path.join(emu, "_build", name)
+    want = g.source_hash(list(sources) + [os.path.join(emu, "hip", "hip_runtime.h"), runtime], flags)
+    if not (os.path.exists(out) and os.path.exists(out + ".stamp") and open(out + ".stamp").read().strip() == want):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        clang = os.environ.get("EMU_CXX", "/opt/rocm/lib/llvm/bin/clang++")
+        subprocess.check_call([clang] + flags + ["-I", emu, "-o", out, sources[0], runtime], cwd=os.path.dirname(sources[0]))
+        with open(out + ".stamp", "w") as fh:
+            fh.write(want)
+    return out
+
+
 def make_cfg_variant(variant="train", num_envs=16, extra=None):
     cfg = apply_train_config(make_cfg(), num_envs=num_envs)
     if variant != "train_noise":

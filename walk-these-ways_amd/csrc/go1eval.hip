@@ -23,29 +23,20 @@
 // launch whose blocks each belong to one joint, so the joint's limits are uniform per block and every row access is a contiguous run
 // (the histogram word alone is scattered); metric rows through reduce_metric_row, the histogram by its own uint64 sums.  tests/joint_ref.py.
 //
-// What the six families share is written once, in the first namespace below: Args (a kernel's one argument: config and buffers by
-// value), Row (a row of an SoA buffer at the thread's environment; TraceAt is the trace's), fold and clear_rows (the six
-// accumulators of a metric row), tree_reduce (the fixed binary tree in LDS), group_sums and reduce_metric_row (the strided pass in
-// front of it: sums over a group's members, and a metric row), Once (one fp32 value per member seen as accumulators that folded it
-// once), status_row and values_table_row (the tables of the response and the recovery).  The entry points at the end share
-// has_accumulators, has_table and launch; what a family validates beyond them stays with the family, in the header's order of codes.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
+// What the six families share with the foot and trunk libraries is written once in go1_tables.h: Args, Row, row_thread, fold and
+// clear_rows (the six accumulators of a metric row), tree_reduce, group_sums and reduce_metric_row (the fixed-order reduction), and
+// the entry points' env_grid, row_grid, table_grid, launch, has_accumulators, has_table and positive.  What only these families use
+// is in the first namespace below: TraceArgs (TraceAt is the trace's Row), Once (one fp32 value per member seen as accumulators that
+// folded it once), status_row and values_table_row (the tables of the response and the recovery), and the quaternion helpers.  What
+// a family validates beyond the shared checks stays with the family, in the header's order of codes.
 #include "../../include/go1eval.h"
+#include "go1_tables.h"
 
 namespace {
 
-constexpr int ACC_THREADS = 256;
-constexpr int NM = GO1EVAL_NUM_METRICS, NF = GO1EVAL_NUM_FIELDS, RT = GO1EVAL_REDUCE_THREADS;
+constexpr int NM = GO1EVAL_NUM_METRICS;
+GO1_TABLES_MATCH(GO1EVAL);
 
-// a kernel's one argument: the caller's config and buffers, by value
-template <class C, class B>
-struct Args {
-  C c;
-  B b;
-};
 using EvalArgs = Args<Go1EvalConfig, Go1EvalBuffers>;
 using BehaviourArgs = Args<Go1BehaviourConfig, Go1BehaviourBuffers>;
 using ResponseArgs = Args<Go1ResponseConfig, Go1ResponseBuffers>;
@@ -58,83 +49,6 @@ struct TraceArgs {
   Go1TraceBuffers b;
   int row;
 };
-
-// row k of an SoA buffer ([k][N]) at environment e
-struct Row {
-  int N, e;
-  __device__ __forceinline__ float operator()(const float* p, int k) const { return p[(size_t)k * N + e]; }
-};
-
-// rows first_row ... first_row + rows - 1 of the accumulators of environment e: nothing folded yet
-template <class Buffers>
-__device__ __forceinline__ void clear_rows(const Buffers& b, int first_row, int rows, int N, int e) {
-  for (int m = 0; m < rows; m++) {
-    const size_t i = (size_t)(first_row + m) * N + e;
-    b.count[i] = 0u; b.nonfinite[i] = 0u; b.sum[i] = 0.0; b.sumsq[i] = 0.0; b.min[i] = INFINITY; b.max[i] = -INFINITY;
-  }
-}
-
-template <class Buffers>
-__device__ __forceinline__ void fold(const Buffers& b, int m, int N, int e, float v) {
-  const size_t i = (size_t)m * N + e;
-  if (!isfinite(v)) { b.nonfinite[i] += 1u; return; }
-  b.count[i] += 1u;
-  b.sum[i] += (double)v;
-  b.sumsq[i] += (double)v * (double)v;
-  b.min[i] = fminf(b.min[i], v);
-  b.max[i] = fmaxf(b.max[i], v);
-}
-
-// the binary tree of fixed shape over the partial results of a workgroup of RT threads, thread t's in lds[f][t]: sums in rows
-// 0 ... F - 1 and, with MinMax, a minimum in row F and a maximum in row F + 1.  Afterwards lds[f][0] holds the workgroup's.
-template <int F, bool MinMax = false>
-__device__ __forceinline__ void tree_reduce(double (*lds)[RT], int t) {
-  __syncthreads();
-  for (int s = RT / 2; s > 0; s >>= 1) {
-    if (t < s) {
-      for (int f = 0; f < F; f++) lds[f][t] += lds[f][t + s];
-      if (MinMax) { lds[F][t] = fmin(lds[F][t], lds[F][t + s]); lds[F + 1][t] = fmax(lds[F + 1][t], lds[F + 1][t + s]); }
-    }
-    __syncthreads();
-  }
-}
-
-// F sums over the members of group g, by one workgroup of RT threads: thread t adds term(e, a) for the members e = t, t + RT, ...
-// in ascending order, then the tree; lds[f][0] holds sum f
-template <int F, class Term>
-__device__ __forceinline__ void group_sums(const int32_t* group, int g, int N, double (*lds)[RT], Term term) {
-  const int t = (int)threadIdx.x;
-  double a[F] = {};
-  for (int e = t; e < N; e += RT) {
-    if (group[e] != g) continue;
-    term(e, a);
-  }
-  for (int f = 0; f < F; f++) lds[f][t] = a[f];
-  tree_reduce<F>(lds, t);
-}
-
-// one metric row of a result table, by one workgroup of RT threads: thread t combines the group's environments t, t + RT, ... in
-// ascending order, then the binary tree in LDS; thread 0 writes the six fields.  a0 count, a1 nonfinite, a2 sum, a3 sumsq, a4 min, a5 max
-template <class Buffers>
-__device__ __forceinline__ void reduce_metric_row(const Buffers& b, int g, int m, int N, double (*lds)[RT], double* out) {
-  const int t = (int)threadIdx.x;
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = (double)INFINITY, a5 = -(double)INFINITY;
-  for (int e = t; e < N; e += RT) {
-    if (b.group[e] != g) continue;
-    const size_t i = (size_t)m * N + e;
-    a0 += (double)b.count[i]; a1 += (double)b.nonfinite[i]; a2 += b.sum[i]; a3 += b.sumsq[i];
-    if (b.count[i] > 0u) { a4 = fmin(a4, (double)b.min[i]); a5 = fmax(a5, (double)b.max[i]); }
-  }
-  lds[0][t] = a0; lds[1][t] = a1; lds[2][t] = a2; lds[3][t] = a3; lds[4][t] = a4; lds[5][t] = a5;
-  tree_reduce<4, true>(lds, t);
-  if (t != 0) return;
-  const double nan = (double)NAN;
-  const double n = lds[0][0];
-  const double mean = n > 0.0 ? lds[2][0] / n : nan;
-  const double var = n > 0.0 ? lds[3][0] / n - mean * mean : nan;
-  out[GO1EVAL_F_COUNT] = n; out[GO1EVAL_F_MEAN] = mean; out[GO1EVAL_F_STD] = n > 0.0 ? sqrt(fmax(var, 0.0)) : nan;
-  out[GO1EVAL_F_MIN] = n > 0.0 ? lds[4][0] : nan; out[GO1EVAL_F_MAX] = n > 0.0 ? lds[5][0] : nan; out[GO1EVAL_F_NONFINITE] = lds[1][0];
-}
 
 // one fp32 value per member, value(i), seen as the accumulators of a member that folded the one value: what reduce_metric_row reads
 template <class V>
@@ -735,19 +649,12 @@ __device__ __forceinline__ int joint_bin(float x, float L, int bins) {
   const float b = floorf((x / L + 1.0f) * 4.0f), last = (float)(bins - 1);
   return (int)(b > last ? last : (b > 0.0f ? b : 0.0f));
 }
-// the launch of one thread per (joint, environment): block k is joint k / blocks_per_joint, its lanes consecutive environments
-__device__ __forceinline__ bool joint_thread(int N, int* j, int* e) {
-  const int per_joint = (N + ACC_THREADS - 1) / ACC_THREADS;
-  *j = (int)blockIdx.x / per_joint;
-  *e = ((int)blockIdx.x % per_joint) * ACC_THREADS + (int)threadIdx.x;
-  return *j < DOF && *e < N;
-}
 }  // namespace
 
 extern "C" __global__ void __launch_bounds__(ACC_THREADS) joint_clear_kernel(const JointArgs A) {
   const int N = A.c.num_envs;
   int j, e;
-  if (!joint_thread(N, &j, &e)) return;
+  if (!row_thread(N, DOF, &j, &e)) return;                      // (block k is joint k / blocks_per_joint)
   const Go1JointBuffers& b = A.b;
   clear_rows(b, j * NJ, NJ, N, e);
   for (int cell = 0; cell < CELLS; cell++) b.hist[(size_t)(j * CELLS + cell) * N + e] = 0u;
@@ -759,7 +666,7 @@ extern "C" __global__ void __launch_bounds__(ACC_THREADS) joint_accumulate_kerne
   const Go1JointConfig& c = A.c;
   const int N = c.num_envs;
   int j, e;
-  if (!joint_thread(N, &j, &e)) return;
+  if (!row_thread(N, DOF, &j, &e)) return;                      // (block k is joint k / blocks_per_joint)
   const Go1JointBuffers& b = A.b;
   const size_t i = (size_t)j * N + e;
   const bool reset = b.reset_buf[e] != 0;
@@ -829,25 +736,7 @@ extern "C" __global__ void __launch_bounds__(RT) joint_reduce_kernel(const Joint
 
 // ---- the entry points: validation in the order the header gives the codes, then one launch -------------------------------------------
 namespace {
-dim3 env_grid(int n) { return dim3((unsigned)((n + ACC_THREADS - 1) / ACC_THREADS)); }
-dim3 joint_grid(int n) { return dim3((unsigned)(DOF * ((n + ACC_THREADS - 1) / ACC_THREADS))); }
-dim3 table_grid(int groups, int rows) { return dim3((unsigned)(groups * rows)); }
-
-template <class A>
-int launch_args(void (*kernel)(A), dim3 grid, int block, void* stream, const A& args) {
-  hipLaunchKernelGGL(kernel, grid, dim3(block), 0, (hipStream_t)stream, args);
-  return hipGetLastError() == hipSuccess ? 0 : -20;
-}
-template <class C, class B>
-int launch(void (*kernel)(Args<C, B>), dim3 grid, int block, void* stream, const C* cfg, const B* buf) {
-  Args<C, B> A; A.c = *cfg; A.b = *buf;
-  return launch_args(kernel, grid, block, stream, A);
-}
-
-template <class B> bool has_accumulators(const B* buf) { return buf->count && buf->sum && buf->sumsq && buf->min && buf->max && buf->nonfinite; }
-template <class C, class B> bool has_table(const C* cfg, const B* buf) { return cfg->num_groups > 0 && buf->group && buf->results; }      // else -5
 template <class C, class B> bool heights_without_points(const C* cfg, const B* buf) { return buf->measured_heights && cfg->num_height_points <= 0; }   // -4
-bool positive(float x) { return x > 0.0f && x <= 3.402823466e38f; }            // finite and positive (a NaN fails both)
 
 // what every entry point of a family asks first: -1, -2 (and the response's -10 for a signal count outside the config's array)
 int check(const Go1EvalConfig* cfg, const Go1EvalBuffers* buf) {
@@ -1000,7 +889,7 @@ extern "C" int go1eval_terrain_reduce(const Go1TerrainConfig* cfg, const Go1Terr
 extern "C" int go1eval_joint_clear(const Go1JointConfig* cfg, const Go1JointBuffers* buf, void* stream) {
   if (int rc = check(cfg, buf)) return rc;
   if (!buf->dof_vel) return -3;
-  return launch(joint_clear_kernel, joint_grid(cfg->num_envs), ACC_THREADS, stream, cfg, buf);
+  return launch(joint_clear_kernel, row_grid(DOF, cfg->num_envs), ACC_THREADS, stream, cfg, buf);
 }
 
 extern "C" int go1eval_joint_accumulate(const Go1JointConfig* cfg, const Go1JointBuffers* buf, void* stream) {
@@ -1010,7 +899,7 @@ extern "C" int go1eval_joint_accumulate(const Go1JointConfig* cfg, const Go1Join
   for (int j = 0; j < DOF; j++) {
     if (!(positive(cfg->torque_limit[j]) && positive(cfg->vel_limit[j]) && cfg->pos_lower[j] <= cfg->pos_upper[j])) return -12;
   }
-  return launch(joint_accumulate_kernel, joint_grid(cfg->num_envs), ACC_THREADS, stream, cfg, buf);
+  return launch(joint_accumulate_kernel, row_grid(DOF, cfg->num_envs), ACC_THREADS, stream, cfg, buf);
 }
 
 extern "C" int go1eval_joint_reduce(const Go1JointConfig* cfg, const Go1JointBuffers* buf, void* stream) {

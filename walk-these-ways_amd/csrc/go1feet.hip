@@ -8,88 +8,19 @@
 // combines environments t, t + 256, ... in ascending order in fp64, then a binary tree of fixed shape in LDS.
 // tests/feet_ref.py restates both in numpy from the header's text.
 //
-// The library shares no source with libgo1eval (its surface and stamp stay as they are): the fold of a value into the six
-// accumulators, the clear, the reduction tree and the validation and launch helpers are restated here by go1eval.hip's rules.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
+// The fold of a value into the six accumulators, the clear, the launch of one thread per (row, environment), the fixed-order reductions
+// (a metric row, the sums of a group row, the sums per bin of the profile) and the validation and launch helpers are go1_tables.h's,
+// shared with the evaluation and trunk libraries.  The library's surface, symbols and stamp remain its own: the stamp covers that header.
 #include "../../include/go1feet.h"
+#include "go1_tables.h"
 
 namespace {
 
-constexpr int ACC_THREADS = 256;
-constexpr int NM = GO1FEET_NUM, FEET = GO1FEET_NUM_FEET, BINS = GO1FEET_PHASE_BINS, NF = GO1FEET_NUM_FIELDS, RT = GO1FEET_REDUCE_THREADS;
-constexpr int SLICES = RT / BINS;
-static_assert(RT == 256 && BINS == 16, "feet_reduce_kernel: sixteen slices of environments per profile bin");
+constexpr int NM = GO1FEET_NUM, FEET = GO1FEET_NUM_FEET;
+GO1_TABLES_MATCH(GO1FEET);
+static_assert(GO1FEET_PHASE_BINS == BINS, "feet_reduce_kernel: the profile's bins are bin_sums'");
 
-// a kernel's one argument: the caller's config and buffers, by value
-struct FeetArgs {
-  Go1FeetConfig c;
-  Go1FeetBuffers b;
-};
-
-// rows first_row ... first_row + rows - 1 of the accumulators of environment e: nothing folded yet
-__device__ __forceinline__ void clear_rows(const Go1FeetBuffers& b, int first_row, int rows, int N, int e) {
-  for (int m = 0; m < rows; m++) {
-    const size_t i = (size_t)(first_row + m) * N + e;
-    b.count[i] = 0u; b.nonfinite[i] = 0u; b.sum[i] = 0.0; b.sumsq[i] = 0.0; b.min[i] = INFINITY; b.max[i] = -INFINITY;
-  }
-}
-
-__device__ __forceinline__ void fold(const Go1FeetBuffers& b, int m, int N, int e, float v) {
-  const size_t i = (size_t)m * N + e;
-  if (!isfinite(v)) { b.nonfinite[i] += 1u; return; }
-  b.count[i] += 1u;
-  b.sum[i] += (double)v;
-  b.sumsq[i] += (double)v * (double)v;
-  b.min[i] = fminf(b.min[i], v);
-  b.max[i] = fmaxf(b.max[i], v);
-}
-
-// the binary tree of fixed shape over the partial results of a workgroup of RT threads, thread t's in lds[f][t]: sums in rows
-// 0 ... F - 1 and, with MinMax, a minimum in row F and a maximum in row F + 1.  Afterwards lds[f][0] holds the workgroup's.
-template <int F, bool MinMax = false>
-__device__ __forceinline__ void tree_reduce(double (*lds)[RT], int t) {
-  __syncthreads();
-  for (int s = RT / 2; s > 0; s >>= 1) {
-    if (t < s) {
-      for (int f = 0; f < F; f++) lds[f][t] += lds[f][t + s];
-      if (MinMax) { lds[F][t] = fmin(lds[F][t], lds[F][t + s]); lds[F + 1][t] = fmax(lds[F + 1][t], lds[F + 1][t + s]); }
-    }
-    __syncthreads();
-  }
-}
-
-// one metric row of the result table, by one workgroup of RT threads: thread t combines the group's environments t, t + RT, ... in
-// ascending order, then the tree; thread 0 writes the six fields.  a0 count, a1 nonfinite, a2 sum, a3 sumsq, a4 min, a5 max
-__device__ __forceinline__ void reduce_metric_row(const Go1FeetBuffers& b, int g, int m, int N, double (*lds)[RT], double* out) {
-  const int t = (int)threadIdx.x;
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = (double)INFINITY, a5 = -(double)INFINITY;
-  for (int e = t; e < N; e += RT) {
-    if (b.group[e] != g) continue;
-    const size_t i = (size_t)m * N + e;
-    a0 += (double)b.count[i]; a1 += (double)b.nonfinite[i]; a2 += b.sum[i]; a3 += b.sumsq[i];
-    if (b.count[i] > 0u) { a4 = fmin(a4, (double)b.min[i]); a5 = fmax(a5, (double)b.max[i]); }
-  }
-  lds[0][t] = a0; lds[1][t] = a1; lds[2][t] = a2; lds[3][t] = a3; lds[4][t] = a4; lds[5][t] = a5;
-  tree_reduce<4, true>(lds, t);
-  if (t != 0) return;
-  const double nan = (double)NAN;
-  const double n = lds[0][0];
-  const double mean = n > 0.0 ? lds[2][0] / n : nan;
-  const double var = n > 0.0 ? lds[3][0] / n - mean * mean : nan;
-  out[GO1FEET_F_COUNT] = n; out[GO1FEET_F_MEAN] = mean; out[GO1FEET_F_STD] = n > 0.0 ? sqrt(fmax(var, 0.0)) : nan;
-  out[GO1FEET_F_MIN] = n > 0.0 ? lds[4][0] : nan; out[GO1FEET_F_MAX] = n > 0.0 ? lds[5][0] : nan; out[GO1FEET_F_NONFINITE] = lds[1][0];
-}
-
-// the launch of one thread per (foot, environment): block k is foot k / blocks_per_foot, its lanes consecutive environments
-__device__ __forceinline__ bool foot_thread(int N, int* f, int* e) {
-  const int per_foot = (N + ACC_THREADS - 1) / ACC_THREADS;
-  *f = (int)blockIdx.x / per_foot;
-  *e = ((int)blockIdx.x % per_foot) * ACC_THREADS + (int)threadIdx.x;
-  return *f < FEET && *e < N;
-}
+using FeetArgs = Args<Go1FeetConfig, Go1FeetBuffers>;
 
 // the profile bin of the finite phase ph: clamped as a float, then converted (see the header)
 __device__ __forceinline__ int phase_bin(float ph) {
@@ -102,7 +33,7 @@ __device__ __forceinline__ int phase_bin(float ph) {
 extern "C" __global__ void __launch_bounds__(ACC_THREADS) feet_clear_kernel(const FeetArgs A) {
   const int N = A.c.num_envs;
   int f, e;
-  if (!foot_thread(N, &f, &e)) return;
+  if (!row_thread(N, FEET, &f, &e)) return;                               // (block k is foot k / blocks_per_foot)
   const Go1FeetBuffers& b = A.b;
   const size_t i = (size_t)f * N + e;
   clear_rows(b, f * NM, NM, N, e);
@@ -119,7 +50,7 @@ extern "C" __global__ void __launch_bounds__(ACC_THREADS) feet_accumulate_kernel
   const Go1FeetConfig& c = A.c;
   const int N = c.num_envs;
   int f, e;
-  if (!foot_thread(N, &f, &e)) return;
+  if (!row_thread(N, FEET, &f, &e)) return;                               // (block k is foot k / blocks_per_foot)
   const Go1FeetBuffers& b = A.b;
   const size_t i = (size_t)f * N + e;
   const bool reset = b.reset_buf[e] != 0;
@@ -200,14 +131,8 @@ extern "C" __global__ void __launch_bounds__(RT) feet_reduce_kernel(const FeetAr
     const int g = (int)blockIdx.x / rows, m = (int)blockIdx.x % rows;
     double* out = b.results + ((size_t)g * rows + m) * NF;
     if (m != rows - 1) { reduce_metric_row(b, g, m, N, lds, out); return; }
-    // the group's own row: environments, steps, resets
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-    for (int e = t; e < N; e += RT) {
-      if (b.group[e] != g) continue;
-      a0 += 1.0; a1 += (double)b.steps[e]; a2 += (double)b.resets[e];
-    }
-    lds[0][t] = a0; lds[1][t] = a1; lds[2][t] = a2;
-    tree_reduce<3>(lds, t);
+    // the group's own row: a[0] envs, a[1] steps, a[2] resets
+    group_sums<3>(b.group, g, N, lds, [&b](int e, double* a) { a[0] += 1.0; a[1] += (double)b.steps[e]; a[2] += (double)b.resets[e]; });
     if (t != 0) return;
     out[GO1FEET_G_ENVS] = lds[0][0]; out[GO1FEET_G_STEPS] = lds[1][0]; out[GO1FEET_G_RESETS] = lds[2][0];
     out[3] = 0.0; out[4] = 0.0; out[5] = 0.0;
@@ -215,19 +140,9 @@ extern "C" __global__ void __launch_bounds__(RT) feet_reduce_kernel(const FeetAr
   }
   // the profile of (group, foot): thread t owns bin t % 16 and the environments t / 16, t / 16 + 16, ...
   const int k = (int)blockIdx.x - G * rows;
-  const int g = k / FEET, f = k % FEET, bin = t % BINS;
-  const size_t w = (size_t)(f * BINS + bin) * N;
-  double sum = 0.0, count = 0.0;
-  for (int e = t / BINS; e < N; e += SLICES) {
-    if (b.group[e] != g) continue;
-    sum += b.profile_sum[w + e]; count += (double)b.profile_count[w + e];
-  }
-  lds[0][t] = sum; lds[1][t] = count;
-  __syncthreads();
-  for (int s = RT / 2; s >= BINS; s >>= 1) {
-    if (t < s) { lds[0][t] += lds[0][t + s]; lds[1][t] += lds[1][t + s]; }
-    __syncthreads();
-  }
+  const int g = k / FEET, f = k % FEET;
+  const size_t w = (size_t)(f * BINS + t % BINS) * N;
+  bin_sums<2>(b.group, g, N, lds, [&b, w](int e, double* a) { a[0] += b.profile_sum[w + e]; a[1] += (double)b.profile_count[w + e]; });
   if (t < BINS) {
     double* out = b.profile_results + (((size_t)g * FEET + f) * BINS + t) * 2;
     out[0] = lds[0][t]; out[1] = lds[1][t];
@@ -236,29 +151,18 @@ extern "C" __global__ void __launch_bounds__(RT) feet_reduce_kernel(const FeetAr
 
 // ---- the entry points: validation in the order the header gives the codes, then one launch ---------------------------------------------
 namespace {
-dim3 foot_grid(int n) { return dim3((unsigned)(FEET * ((n + ACC_THREADS - 1) / ACC_THREADS))); }
-
-int launch(void (*kernel)(FeetArgs), dim3 grid, int block, void* stream, const Go1FeetConfig* cfg, const Go1FeetBuffers* buf) {
-  FeetArgs A; A.c = *cfg; A.b = *buf;
-  hipLaunchKernelGGL(kernel, grid, dim3(block), 0, (hipStream_t)stream, A);
-  return hipGetLastError() == hipSuccess ? 0 : -20;
-}
-
-bool finite(float x) { return x >= -3.402823466e38f && x <= 3.402823466e38f; }        // (a NaN fails both)
-
 // what every entry point asks first: -1, -2
 int check(const Go1FeetConfig* cfg, const Go1FeetBuffers* buf) {
   if (!cfg || !buf || cfg->num_envs <= 0) return -1;
-  if (!buf->count || !buf->sum || !buf->sumsq || !buf->min || !buf->max || !buf->nonfinite || !buf->prev_contact || !buf->stance_valid ||
-      !buf->stance_steps || !buf->stance_peak || !buf->stance_impulse || !buf->stance_slip || !buf->steps || !buf->resets ||
-      !buf->profile_sum || !buf->profile_count) return -2;
+  if (!has_accumulators(buf) || !buf->prev_contact || !buf->stance_valid || !buf->stance_steps || !buf->stance_peak || !buf->stance_impulse ||
+      !buf->stance_slip || !buf->steps || !buf->resets || !buf->profile_sum || !buf->profile_count) return -2;
   return 0;
 }
 }  // namespace
 
 extern "C" int go1feet_clear(const Go1FeetConfig* cfg, const Go1FeetBuffers* buf, void* stream) {
   if (int rc = check(cfg, buf)) return rc;
-  return launch(feet_clear_kernel, foot_grid(cfg->num_envs), ACC_THREADS, stream, cfg, buf);
+  return launch(feet_clear_kernel, row_grid(FEET, cfg->num_envs), ACC_THREADS, stream, cfg, buf);
 }
 
 extern "C" int go1feet_accumulate(const Go1FeetConfig* cfg, const Go1FeetBuffers* buf, void* stream) {
@@ -267,13 +171,13 @@ extern "C" int go1feet_accumulate(const Go1FeetConfig* cfg, const Go1FeetBuffers
       !buf->reset_buf || !buf->episode_length_buf) return -3;
   if (!(finite(cfg->dt) && cfg->dt > 0.0f && finite(cfg->terrain_friction) && cfg->terrain_friction >= 0.0f && finite(cfg->max_contact_force)))
     return -12;
-  return launch(feet_accumulate_kernel, foot_grid(cfg->num_envs), ACC_THREADS, stream, cfg, buf);
+  return launch(feet_accumulate_kernel, row_grid(FEET, cfg->num_envs), ACC_THREADS, stream, cfg, buf);
 }
 
 extern "C" int go1feet_reduce(const Go1FeetConfig* cfg, const Go1FeetBuffers* buf, void* stream) {
   if (int rc = check(cfg, buf)) return rc;
-  if (cfg->num_groups <= 0 || !buf->group || !buf->results || !buf->profile_results) return -5;
-  return launch(feet_reduce_kernel, dim3((unsigned)(cfg->num_groups * (FEET * NM + 1 + FEET))), RT, stream, cfg, buf);
+  if (!has_table(cfg, buf) || !buf->profile_results) return -5;
+  return launch(feet_reduce_kernel, table_grid(cfg->num_groups, FEET * NM + 1 + FEET), RT, stream, cfg, buf);
 }
 
 #ifndef GO1_SOURCE_HASH

@@ -9,72 +9,19 @@
 // combines environments t, t + 256, ... in ascending order in fp64, then a binary tree of fixed shape in LDS.
 // tests/trunk_ref.py restates both in numpy from the header's text.
 //
-// The library shares no source with the other libraries: the fold of a value into the six accumulators, the clear, the reduction tree
-// and the validation and launch helpers are restated here by the evaluation library's rules.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
-
+// The fold of a value into the six accumulators, the clear, the fixed-order reductions (a metric row, the sums of a group row, the sums
+// per bin of the histogram) and the validation and launch helpers are go1_tables.h's, shared with the evaluation and foot libraries.
+// The library's surface, symbols and stamp remain its own: the stamp covers that header.
 #include "../../include/go1trunk.h"
+#include "go1_tables.h"
 
 namespace {
 
-constexpr int ACC_THREADS = 256;
-constexpr int NM = GO1TRUNK_NUM, BINS = GO1TRUNK_TILT_BINS, NF = GO1TRUNK_NUM_FIELDS, RT = GO1TRUNK_REDUCE_THREADS;
-constexpr int SLICES = RT / BINS;
-static_assert(RT == 256 && BINS == 16, "trunk_reduce_kernel: sixteen slices of environments per histogram bin");
+constexpr int NM = GO1TRUNK_NUM;
+GO1_TABLES_MATCH(GO1TRUNK);
+static_assert(GO1TRUNK_TILT_BINS == BINS, "trunk_reduce_kernel: the histogram's bins are bin_sums'");
 
-// a kernel's one argument: the caller's config and buffers, by value
-struct TrunkArgs {
-  Go1TrunkConfig c;
-  Go1TrunkBuffers b;
-};
-
-__device__ __forceinline__ void fold(const Go1TrunkBuffers& b, int m, int N, int e, float v) {
-  const size_t i = (size_t)m * N + e;
-  if (!isfinite(v)) { b.nonfinite[i] += 1u; return; }
-  b.count[i] += 1u;
-  b.sum[i] += (double)v;
-  b.sumsq[i] += (double)v * (double)v;
-  b.min[i] = fminf(b.min[i], v);
-  b.max[i] = fmaxf(b.max[i], v);
-}
-
-// the binary tree of fixed shape over the partial results of a workgroup of RT threads, thread t's in lds[f][t]: sums in rows
-// 0 ... F - 1 and, with MinMax, a minimum in row F and a maximum in row F + 1.  Afterwards lds[f][0] holds the workgroup's.
-template <int F, bool MinMax = false>
-__device__ __forceinline__ void tree_reduce(double (*lds)[RT], int t) {
-  __syncthreads();
-  for (int s = RT / 2; s > 0; s >>= 1) {
-    if (t < s) {
-      for (int f = 0; f < F; f++) lds[f][t] += lds[f][t + s];
-      if (MinMax) { lds[F][t] = fmin(lds[F][t], lds[F][t + s]); lds[F + 1][t] = fmax(lds[F + 1][t], lds[F + 1][t + s]); }
-    }
-    __syncthreads();
-  }
-}
-
-// one metric row of the result table, by one workgroup of RT threads: thread t combines the group's environments t, t + RT, ... in
-// ascending order, then the tree; thread 0 writes the six fields.  a0 count, a1 nonfinite, a2 sum, a3 sumsq, a4 min, a5 max
-__device__ __forceinline__ void reduce_metric_row(const Go1TrunkBuffers& b, int g, int m, int N, double (*lds)[RT], double* out) {
-  const int t = (int)threadIdx.x;
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0, a4 = (double)INFINITY, a5 = -(double)INFINITY;
-  for (int e = t; e < N; e += RT) {
-    if (b.group[e] != g) continue;
-    const size_t i = (size_t)m * N + e;
-    a0 += (double)b.count[i]; a1 += (double)b.nonfinite[i]; a2 += b.sum[i]; a3 += b.sumsq[i];
-    if (b.count[i] > 0u) { a4 = fmin(a4, (double)b.min[i]); a5 = fmax(a5, (double)b.max[i]); }
-  }
-  lds[0][t] = a0; lds[1][t] = a1; lds[2][t] = a2; lds[3][t] = a3; lds[4][t] = a4; lds[5][t] = a5;
-  tree_reduce<4, true>(lds, t);
-  if (t != 0) return;
-  const double nan = (double)NAN;
-  const double n = lds[0][0];
-  const double mean = n > 0.0 ? lds[2][0] / n : nan;
-  const double var = n > 0.0 ? lds[3][0] / n - mean * mean : nan;
-  out[GO1TRUNK_F_COUNT] = n; out[GO1TRUNK_F_MEAN] = mean; out[GO1TRUNK_F_STD] = n > 0.0 ? sqrt(fmax(var, 0.0)) : nan;
-  out[GO1TRUNK_F_MIN] = n > 0.0 ? lds[4][0] : nan; out[GO1TRUNK_F_MAX] = n > 0.0 ? lds[5][0] : nan; out[GO1TRUNK_F_NONFINITE] = lds[1][0];
-}
+using TrunkArgs = Args<Go1TrunkConfig, Go1TrunkBuffers>;
 
 // the histogram bin of the finite tilt: clamped as a float, then converted (see the header)
 __device__ __forceinline__ int tilt_bin(float tilt) {
@@ -95,10 +42,7 @@ extern "C" __global__ void __launch_bounds__(ACC_THREADS) trunk_clear_kernel(con
   const int e = (int)blockIdx.x * ACC_THREADS + (int)threadIdx.x;
   if (e >= N) return;
   const Go1TrunkBuffers& b = A.b;
-  for (int m = 0; m < NM; m++) {
-    const size_t i = (size_t)m * N + e;
-    b.count[i] = 0u; b.nonfinite[i] = 0u; b.sum[i] = 0.0; b.sumsq[i] = 0.0; b.min[i] = INFINITY; b.max[i] = -INFINITY;
-  }
+  clear_rows(b, 0, NM, N, e);
   for (int bin = 0; bin < BINS; bin++) b.tilt_hist[(size_t)bin * N + e] = 0u;
   b.prev_valid[e] = 0; b.seg_valid[e] = 0; b.seg_steps[e] = 0;
   for (int k = 0; k < 3; k++) { b.prev_lin_vel[(size_t)k * N + e] = 0.0f; b.prev_ang_vel[(size_t)k * N + e] = 0.0f; }
@@ -233,54 +177,29 @@ extern "C" __global__ void __launch_bounds__(RT) trunk_reduce_kernel(const Trunk
     const int g = (int)blockIdx.x / rows, m = (int)blockIdx.x % rows;
     double* out = b.results + ((size_t)g * rows + m) * NF;
     if (m != rows - 1) { reduce_metric_row(b, g, m, N, lds, out); return; }
-    // the group's own row: environments, steps, resets, segments dropped
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-    for (int e = t; e < N; e += RT) {
-      if (b.group[e] != g) continue;
-      a0 += 1.0; a1 += (double)b.steps[e]; a2 += (double)b.resets[e]; a3 += (double)b.segments_dropped[e];
-    }
-    lds[0][t] = a0; lds[1][t] = a1; lds[2][t] = a2; lds[3][t] = a3;
-    tree_reduce<4>(lds, t);
+    // the group's own row: a[0] envs, a[1] steps, a[2] resets, a[3] segments dropped
+    group_sums<4>(b.group, g, N, lds, [&b](int e, double* a) {
+      a[0] += 1.0; a[1] += (double)b.steps[e]; a[2] += (double)b.resets[e]; a[3] += (double)b.segments_dropped[e];
+    });
     if (t != 0) return;
     out[GO1TRUNK_G_ENVS] = lds[0][0]; out[GO1TRUNK_G_STEPS] = lds[1][0]; out[GO1TRUNK_G_RESETS] = lds[2][0];
     out[GO1TRUNK_G_SEGMENTS_DROPPED] = lds[3][0]; out[4] = 0.0; out[5] = 0.0;
     return;
   }
   // the tilt histogram of a group: thread t owns bin t % 16 and the environments t / 16, t / 16 + 16, ...
-  const int g = (int)blockIdx.x - G * rows, bin = t % BINS;
-  const size_t w = (size_t)bin * N;
-  double count = 0.0;
-  for (int e = t / BINS; e < N; e += SLICES) {
-    if (b.group[e] != g) continue;
-    count += (double)b.tilt_hist[w + e];
-  }
-  lds[0][t] = count;
-  __syncthreads();
-  for (int s = RT / 2; s >= BINS; s >>= 1) {
-    if (t < s) lds[0][t] += lds[0][t + s];
-    __syncthreads();
-  }
+  const int g = (int)blockIdx.x - G * rows;
+  const size_t w = (size_t)(t % BINS) * N;
+  bin_sums<1>(b.group, g, N, lds, [&b, w](int e, double* a) { a[0] += (double)b.tilt_hist[w + e]; });
   if (t < BINS) b.hist_results[(size_t)g * BINS + t] = lds[0][t];
 }
 
 // ---- the entry points: validation in the order the header gives the codes, then one launch ---------------------------------------------
 namespace {
-dim3 env_grid(int n) { return dim3((unsigned)((n + ACC_THREADS - 1) / ACC_THREADS)); }
-
-int launch(void (*kernel)(TrunkArgs), dim3 grid, int block, void* stream, const Go1TrunkConfig* cfg, const Go1TrunkBuffers* buf) {
-  TrunkArgs A; A.c = *cfg; A.b = *buf;
-  hipLaunchKernelGGL(kernel, grid, dim3(block), 0, (hipStream_t)stream, A);
-  return hipGetLastError() == hipSuccess ? 0 : -20;
-}
-
-bool finite(float x) { return x >= -3.402823466e38f && x <= 3.402823466e38f; }        // (a NaN fails both)
-
 // what every entry point asks first: -1, -2
 int check(const Go1TrunkConfig* cfg, const Go1TrunkBuffers* buf) {
   if (!cfg || !buf || cfg->num_envs <= 0) return -1;
-  if (!buf->count || !buf->sum || !buf->sumsq || !buf->min || !buf->max || !buf->nonfinite || !buf->prev_valid || !buf->prev_lin_vel ||
-      !buf->prev_ang_vel || !buf->seg_valid || !buf->seg_steps || !buf->seg_anchor || !buf->seg_command || !buf->segments_dropped ||
-      !buf->steps || !buf->resets || !buf->tilt_hist) return -2;
+  if (!has_accumulators(buf) || !buf->prev_valid || !buf->prev_lin_vel || !buf->prev_ang_vel || !buf->seg_valid || !buf->seg_steps ||
+      !buf->seg_anchor || !buf->seg_command || !buf->segments_dropped || !buf->steps || !buf->resets || !buf->tilt_hist) return -2;
   return 0;
 }
 }  // namespace
@@ -300,8 +219,8 @@ extern "C" int go1trunk_accumulate(const Go1TrunkConfig* cfg, const Go1TrunkBuff
 
 extern "C" int go1trunk_reduce(const Go1TrunkConfig* cfg, const Go1TrunkBuffers* buf, void* stream) {
   if (int rc = check(cfg, buf)) return rc;
-  if (cfg->num_groups <= 0 || !buf->group || !buf->results || !buf->hist_results) return -5;
-  return launch(trunk_reduce_kernel, dim3((unsigned)(cfg->num_groups * (NM + 1 + 1))), RT, stream, cfg, buf);
+  if (!has_table(cfg, buf) || !buf->hist_results) return -5;
+  return launch(trunk_reduce_kernel, table_grid(cfg->num_groups, NM + 1 + 1), RT, stream, cfg, buf);
 }
 
 #ifndef GO1_SOURCE_HASH

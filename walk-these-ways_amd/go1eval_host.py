@@ -204,26 +204,32 @@ class Go1EvalLibraryMissing(RuntimeError):
     pass
 
 
-def load_library(path=None):
-    """Load libgo1eval.so (HIP, gfx950).  Fails loudly: the metrics kernels have no CPU fallback."""
-    global _lib
-    if path is None and _lib is not None:
-        return _lib
-    p = path or LIB_PATH
+def _load(module, path, missing, what, entry_points, version):
+    """The loader of the three metric libraries.  module: the caller's globals(), whose LIB_PATH is the default path and whose _lib
+    caches the library loaded from it (a library loaded from another path is not cached); missing(...) is raised for an absent file,
+    `what` names in its message what has no CPU fallback; entry_points: (symbols, config, buffers) rows, each symbol
+    f(const config*, const buffers*, void* stream) -> int, go1eval_trace_record alone with the row (int32) in front of the stream."""
+    if path is None and module["_lib"] is not None:
+        return module["_lib"]
+    p = path or module["LIB_PATH"]
     if not os.path.exists(p):
-        raise Go1EvalLibraryMissing(
-            f"{p} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-            f"(hipcc --offload-arch=gfx950). Device-side evaluation metrics have no CPU fallback.")
+        raise missing(f"{p} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                      f"(hipcc --offload-arch=gfx950). Device-side {what} have no CPU fallback.")
     lib = ctypes.CDLL(p)
-    for symbols, config, buffers in _ENTRY_POINTS:
+    for symbols, config, buffers in entry_points:
         for fn in symbols:
             row = [ctypes.c_int32] if fn == "go1eval_trace_record" else []
             getattr(lib, fn).argtypes = [ctypes.POINTER(config), ctypes.POINTER(buffers)] + row + [ctypes.c_void_p]
             getattr(lib, fn).restype = ctypes.c_int
-    lib.go1eval_version.restype = ctypes.c_char_p
+    getattr(lib, version).restype = ctypes.c_char_p
     if path is None:
-        _lib = lib
+        module["_lib"] = lib
     return lib
+
+
+def load_library(path=None):
+    """Load libgo1eval.so (HIP, gfx950).  Fails loudly: the metrics kernels have no CPU fallback."""
+    return _load(globals(), path, Go1EvalLibraryMissing, "evaluation metrics", _ENTRY_POINTS, "go1eval_version")
 
 
 def _groups(groups, count, member="environment"):

@@ -1,10 +1,11 @@
 """Host side of the foot-loading C-ABI (include/go1feet.h): ctypes mirrors, library loading, and `Go1Feet`, which owns the
 per-(foot, environment) accumulators, the stance state, the GRF profile and the three result tables of one simulator instance.
 
-libgo1feet.so is a library of its own (the evaluation library's surface stays as it is), but the host object is the evaluation
-library's accumulating family: `Go1Feet` subclasses `go1eval_host._Table` and hands it its own library, so arm / accumulate /
-disarm / reduce, the group validation and the launch check are the tables'.  `accumulate()` enqueues one launch; the host reads
-the tables when it asks for `read()`.
+libgo1feet.so is a library of its own (the evaluation library's surface stays as it is) whose device code shares
+csrc/go1_tables.h with the evaluation and trunk libraries, and the host side shares as much: `load_library` is
+`go1eval_host._load` with this module's path, cache, error class and entry points, and `Go1Feet` subclasses `go1eval_host._Table`
+and hands it its own library, so arm / accumulate / disarm / reduce, the group validation and the launch check are the tables'.
+`accumulate()` enqueues one launch; the host reads the tables when it asks for `read()`.
 """
 import ctypes
 import os
@@ -12,7 +13,7 @@ import os
 import numpy as np
 import torch
 
-from go1eval_host import NUM_FIELDS, _ACCUMULATORS, _Table
+from go1eval_host import NUM_FIELDS, _ACCUMULATORS, _Table, _load
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libgo1feet.so")
@@ -50,22 +51,8 @@ class Go1FeetLibraryMissing(RuntimeError):
 
 def load_library(path=None):
     """Load libgo1feet.so (HIP, gfx950).  Fails loudly: the foot-loading kernels have no CPU fallback."""
-    global _lib
-    if path is None and _lib is not None:
-        return _lib
-    p = path or LIB_PATH
-    if not os.path.exists(p):
-        raise Go1FeetLibraryMissing(
-            f"{p} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-            f"(hipcc --offload-arch=gfx950). Device-side foot-loading metrics have no CPU fallback.")
-    lib = ctypes.CDLL(p)
-    for fn in ("go1feet_clear", "go1feet_accumulate", "go1feet_reduce"):
-        getattr(lib, fn).argtypes = [ctypes.POINTER(Go1FeetConfig), ctypes.POINTER(Go1FeetBuffers), ctypes.c_void_p]
-        getattr(lib, fn).restype = ctypes.c_int
-    lib.go1feet_version.restype = ctypes.c_char_p
-    if path is None:
-        _lib = lib
-    return lib
+    return _load(globals(), path, Go1FeetLibraryMissing, "foot-loading metrics", [(EXPORTED_SYMBOLS[:3], Go1FeetConfig, Go1FeetBuffers)],
+                 "go1feet_version")
 
 
 def phase_edges():

@@ -1,8 +1,9 @@
 """Host side of the trunk C-ABI (include/go1trunk.h): ctypes mirrors, library loading, and `Go1Trunk`, which owns the per-environment
 accumulators, the velocity and segment state, the tilt histogram and the two result tables of one simulator instance.
 
-libgo1trunk.so is a library of its own (the evaluation library's and the foot library's surfaces stay as they are), but the host object
-is the evaluation library's accumulating family: `Go1Trunk` subclasses `go1eval_host._Table` and hands it its own library, so arm /
+libgo1trunk.so is a library of its own (the evaluation library's and the foot library's surfaces stay as they are) whose device code
+shares csrc/go1_tables.h with those two, and the host side shares as much: `load_library` is `go1eval_host._load` with this module's
+path, cache, error class and entry points, and `Go1Trunk` subclasses `go1eval_host._Table` and hands it its own library, so arm /
 accumulate / disarm / reduce, the group validation and the launch check are the tables'.  `accumulate()` enqueues one launch; the host
 reads the tables when it asks for `read()`.
 """
@@ -12,7 +13,7 @@ import os
 import numpy as np
 import torch
 
-from go1eval_host import _ACCUMULATORS, _Table
+from go1eval_host import _ACCUMULATORS, _Table, _load
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libgo1trunk.so")
@@ -50,22 +51,8 @@ class Go1TrunkLibraryMissing(RuntimeError):
 
 def load_library(path=None):
     """Load libgo1trunk.so (HIP, gfx950).  Fails loudly: the trunk kernels have no CPU fallback."""
-    global _lib
-    if path is None and _lib is not None:
-        return _lib
-    p = path or LIB_PATH
-    if not os.path.exists(p):
-        raise Go1TrunkLibraryMissing(
-            f"{p} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-            f"(hipcc --offload-arch=gfx950). Device-side trunk metrics have no CPU fallback.")
-    lib = ctypes.CDLL(p)
-    for fn in ("go1trunk_clear", "go1trunk_accumulate", "go1trunk_reduce"):
-        getattr(lib, fn).argtypes = [ctypes.POINTER(Go1TrunkConfig), ctypes.POINTER(Go1TrunkBuffers), ctypes.c_void_p]
-        getattr(lib, fn).restype = ctypes.c_int
-    lib.go1trunk_version.restype = ctypes.c_char_p
-    if path is None:
-        _lib = lib
-    return lib
+    return _load(globals(), path, Go1TrunkLibraryMissing, "trunk metrics", [(EXPORTED_SYMBOLS[:3], Go1TrunkConfig, Go1TrunkBuffers)],
+                 "go1trunk_version")
 
 
 def tilt_edges():
