@@ -26,7 +26,9 @@ printed and appended to `<out>/eval/<preset>_response.md`.  `--trace-envs I [I .
 With `--push` every environment trots at 1 m/s and is pushed once with one cell of the `--magnitude M ...` (m/s) x `--direction D ...`
 (degrees in the robot's heading frame: 0 a shove from behind, 90 a push to the left) grid; the trace around the push is recorded
 and analysed on the device (go1_gym_learn.eval_metrics.recovery), `<out>/eval/<preset>_push.json` is written and the recovery table
-is printed and appended to `<out>/eval/<preset>_push.md`.  `--trace-envs I [I ...]` also writes `<preset>_push_trace.npz` and the
+is printed and appended to `<out>/eval/<preset>_push.md`.  `--paired` copies the settled state of the first envs // cells environments
+to all of them first (LeggedRobot.save_state / load_state), so that every cell pushes the same robots at the same instant; with a magnitude-0 cell
+the table gains the paired excess of the peak velocity error over that control.  `--trace-envs I [I ...]` also writes `<preset>_push_trace.npz` and the
 figure of each to `<preset>_push_trace_env<I>.png`.
 
     python tools/eval_sweep.py --checkpoint RUN_DIR/checkpoints --out RUN_DIR --terrain --rows 4 --cols 5 --vx 1.0 --window 500
@@ -143,6 +145,8 @@ def parse_args(argv=None):
     ap.add_argument("--trace-envs", nargs="+", type=int, default=None, help="with --response or --push: environments whose trace and figure are written")
     ap.add_argument("--push", action="store_true", help="measure the recovery from one push per environment over the --magnitude x --direction grid")
     ap.add_argument("--magnitude", nargs="+", type=float, default=None, help="with --push: velocity steps in m/s; 0 is the control cell")
+    ap.add_argument("--paired", action="store_true",
+                    help="with --push: the first envs // cells environments' state after settling is copied to all, so every cell pushes the same robots at the same instant")
     ap.add_argument("--direction", nargs="+", type=float, default=None,
                     help="with --push: directions in degrees in the robot's heading frame (0 a shove from behind, 90 a push to the left)")
     ap.add_argument("--joints", action="store_true", help="measure per-joint actuator usage over the velocity grid, beside the scalar table")
@@ -186,6 +190,8 @@ def parse_args(argv=None):
         ap.error("--trace-envs needs --response or --push")
     if (a.magnitude or a.direction) and not a.push:
         ap.error("--magnitude and --direction need --push")
+    if a.paired and not a.push:
+        ap.error("--paired needs --push")
     if a.push and (a.response or a.behaviour):
         ap.error("--push excludes --response and --behaviour")
     if a.push and not (a.magnitude and a.direction):
@@ -231,7 +237,7 @@ def run_push(a, policy):
     from go1_gym_learn.eval_metrics import recovery, response
     for preset in a.presets:
         res = recovery.run_push_sweep(policy, preset, a.magnitude, a.direction, num_envs=a.envs, seed=a.seed, terrain=a.terrain,
-                                      trace_envs=a.trace_envs)
+                                      trace_envs=a.trace_envs, **(dict(paired=True) if a.paired else {}))
         stem = os.path.join(a.out, "eval", preset)
         with open(stem + "_push.json", "w") as f:
             json.dump(recovery.recovery_to_json(res), f, indent=1)

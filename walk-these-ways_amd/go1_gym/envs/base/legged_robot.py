@@ -155,6 +155,7 @@ class LeggedRobot(BaseTask):
         self._joints = None               # go1eval_host.Go1Joints, created by the first start_joint_metrics()
         self._feet = None                 # go1feet_host.Go1Feet, created by the first start_foot_metrics()
         self._trunk = None                # go1trunk_host.Go1Trunk, created by the first start_trunk_metrics()
+        self._state = None                # go1state_host.Go1State, created by the first save_state() / load_state()
         if eval_cfg is not None:          # reference legged_robot.py:41-42
             self._parse_cfg(eval_cfg)
         self._parse_cfg(cfg)
@@ -807,6 +808,49 @@ class LeggedRobot(BaseTask):
         segments_dropped, "tilt_hist": (groups, 16), "tilt_edges": (17,), the per-environment state and "env_max_tilt"}: one reduction
         launch and the device-to-host copies"""
         return self._started("read_trunk_metrics", "_trunk", "start_trunk_metrics").read()
+
+    # ---- the state (include/go1state.h, libgo1state.so: a library of its own): hold a moment still.  save_state() gathers the full
+    # simulator state of chosen environments into a packed snapshot on the device (one launch), load_state() scatters snapshot rows
+    # into chosen environments (one launch), re-phased to where the lag and history rings stand now.  Neither runs during step(): an
+    # environment that never saves imports nothing.  What a snapshot does not hold: the terrain, the configuration, the host-backend
+    # curriculum objects (device_curriculum=False), and the accumulators of the measurement families.
+    _STATE_FAMILIES = (("metrics", "_metrics"), ("behaviour", "_behaviour"), ("trace", "_trace"), ("terrain", "_traversal"),
+                       ("joints", "_joints"), ("feet", "_feet"), ("trunk", "_trunk"))
+
+    def _stater(self, what):
+        if self._state is None:
+            if self.buffers.device.type != "cuda":
+                raise NotImplementedError(f"{what}(): the state copies are a HIP library; this simulator's buffers are not on a GPU")
+            import go1state_host
+            self._state = go1state_host.Go1State(self.sim_config, self.buffers, self.sim)
+        return self._state
+
+    def save_state(self, env_ids=None):
+        """the full simulator state of the environments `env_ids` (None: all, with the step counter's global companions: curriculum
+        weights and counts, episode log, fault counts) as a go1state_host.SimState on the device.  One launch (two for all) on the
+        simulator's stream; nothing is read to the host, ids given on the host are checked on the host."""
+        return self._stater("save_state").capture(env_ids)
+
+    def load_state(self, state, env_ids=None, rows=None, restore_clock=None):
+        """put row rows[k] (None: k) of `state` into environment env_ids[k] (None: the environments in order).  Rows may repeat: one
+        robot's state fanned out to many environments; the environments must be distinct.  restore_clock (default: for a whole state
+        loaded whole) also restores the global arrays and sets the simulator's and the environment's step counter to the state's, so
+        that the counter-based random streams and the gravity schedule replay; otherwise counters and globals stay as they are and a
+        branched environment's draws after the load are those of its own index.  Refused while a measurement family, a trace or a
+        camera is armed: their accumulators are not part of the state, and a restore is a teleport to them."""
+        stater = self._stater("load_state")
+        armed = [name for name, attr in self._STATE_FAMILIES if getattr(self, attr) is not None and getattr(self, attr).armed]
+        if self._render is not None and self._render.any_armed:
+            armed.append("camera")
+        if armed:
+            raise RuntimeError(f"load_state(): refused while {', '.join(armed)} {'is' if len(armed) == 1 else 'are'} armed: stop "
+                               f"{'it' if len(armed) == 1 else 'them'} first (a restore is a teleport to what they accumulate)")
+        if restore_clock is None:
+            restore_clock = bool(state.whole) and env_ids is None and rows is None
+        stater.restore(state, env_ids, rows, restore_global=bool(restore_clock))
+        if restore_clock:
+            self.sim.set_counters(state.counter, self.sim.counters()[1])
+            self.common_step_counter = int(state.counter)
 
     def render(self, mode="rgb_array"):
         """reference :1612-1620: env 0 from its recording camera, now: (240, 360, 4) uint8 RGBA"""
