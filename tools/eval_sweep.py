@@ -61,6 +61,13 @@ include/go1trunk.h): roll, pitch and tilt, their rates, the trunk's acceleration
 the support polygon, and the lateral drift, heading drift and progress error per straight segment of `--segment-steps` steps;
 `--tilt-limit` is the sine beyond which a step counts as tilted too far.  `<out>/eval/<preset>_trunk.json` and the tilt histogram
 `<preset>_tilt.png` are written and the table is printed and appended to `<preset>_trunk.md`.
+
+    python tools/eval_sweep.py --checkpoint RUN_DIR/checkpoints --out RUN_DIR --rewards --vx 0.5 1.0 1.5
+
+With `--rewards` the velocity grid is swept with the reward table armed beside the scalar one (go1_gym_learn.eval_metrics.rewards,
+include/go1reward.h): the mean scaled reward per step of every active term and its share, their sum, its positive and negative part,
+the total after the clip and what the clip forgave, per cell.  `<out>/eval/<preset>_rewards.json` and the stacked-bar figure
+`<preset>_rewards.png` are written and the table is printed and appended to `<preset>_rewards.md`.
 Run on the GPU box."""
 import argparse
 import json
@@ -154,6 +161,7 @@ def parse_args(argv=None):
     ap.add_argument("--trunk", action="store_true", help="measure trunk motion, support margin and path drift over the velocity grid, beside the scalar table")
     ap.add_argument("--segment-steps", type=int, default=None, help="with --trunk: policy steps of a drift segment, default 50")
     ap.add_argument("--tilt-limit", type=float, default=None, help="with --trunk: the sine of the tilt beyond which a step is counted, default 0.25")
+    ap.add_argument("--rewards", action="store_true", help="break the step reward down by term over the velocity grid, beside the scalar table")
     ap.add_argument("--out", required=True)
     a = ap.parse_args(argv)
     a.tiles = a.terrain == "tiles"
@@ -177,6 +185,8 @@ def parse_args(argv=None):
         ap.error("--feet excludes --terrain (bare), --response, --behaviour, --push and --joints")
     if a.trunk and (a.tiles or a.response or a.behaviour or a.push or a.joints or a.feet):
         ap.error("--trunk excludes --terrain (bare), --response, --behaviour, --push, --joints and --feet")
+    if a.rewards and (a.tiles or a.response or a.behaviour or a.push or a.joints or a.feet or a.trunk):
+        ap.error("--rewards excludes --terrain (bare), --response, --behaviour, --push, --joints, --feet and --trunk")
     if not a.trunk and (a.segment_steps is not None or a.tilt_limit is not None):
         ap.error("--segment-steps and --tilt-limit need --trunk")
     if a.trunk:
@@ -311,6 +321,20 @@ def run_trunk(a, policy, grid):
         trunk.plot_tilt(res, stem + "_tilt.png")
 
 
+def run_rewards(a, policy, grid):
+    from go1_gym_learn.eval_metrics import rewards
+    for preset in a.presets:
+        res = rewards.run_reward_sweep(policy, preset, grid, num_envs=a.envs, steps=a.steps, warmup_steps=a.warmup_steps, seed=a.seed, terrain=a.terrain)
+        stem = os.path.join(a.out, "eval", preset)
+        with open(stem + "_rewards.json", "w") as f:
+            json.dump(rewards.reward_to_json(res), f, indent=1)
+        text = f"### {preset}: {a.envs} environments, {a.steps} steps, vx {a.vx}, reward by term (mean per step, share)\n\n" + rewards.reward_table(res) + "\n"
+        print(text)
+        with open(stem + "_rewards.md", "a") as f:
+            f.write(text + "\n")
+        rewards.plot_reward_shares(res, stem + "_rewards.png")
+
+
 def behaviour_axes(a):
     """{command name: [values]} of the --axis options, in the order given"""
     from go1_gym_learn.eval_metrics.behaviour import COMMAND_INDEX
@@ -343,6 +367,8 @@ def main(argv=None):
         return run_feet(a, policy, grid)
     if a.trunk:
         return run_trunk(a, policy, grid)
+    if a.rewards:
+        return run_rewards(a, policy, grid)
     if a.behaviour:
         from go1_gym_learn.eval_metrics import behaviour
         axes = behaviour_axes(a)

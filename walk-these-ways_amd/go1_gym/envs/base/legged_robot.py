@@ -155,6 +155,7 @@ class LeggedRobot(BaseTask):
         self._joints = None               # go1eval_host.Go1Joints, created by the first start_joint_metrics()
         self._feet = None                 # go1feet_host.Go1Feet, created by the first start_foot_metrics()
         self._trunk = None                # go1trunk_host.Go1Trunk, created by the first start_trunk_metrics()
+        self._reward = None               # go1reward_host.Go1Reward, created by the first start_reward_metrics()
         self._state = None                # go1state_host.Go1State, created by the first save_state() / load_state()
         if eval_cfg is not None:          # reference legged_robot.py:41-42
             self._parse_cfg(eval_cfg)
@@ -460,6 +461,8 @@ class LeggedRobot(BaseTask):
             self._feet.accumulate()
         if self._trunk is not None and self._trunk.armed:
             self._trunk.accumulate()
+        if self._reward is not None and self._reward.armed:
+            self._reward.accumulate(H.gravity_at(self.sim_config, self.common_step_counter))     # (the gravity of the step just taken)
         if self._curriculum_sync and (self.common_step_counter + 1) % self.sim_config.curriculum_update_interval == 0:
             # ONE exchange for the last `curriculum_update_interval` steps' success counts (a slot per step), then the per-step
             # updates in order: every rank applies what a single process over the concatenated shards would
@@ -495,6 +498,8 @@ class LeggedRobot(BaseTask):
             self.sim.reset_idx(torch.as_tensor(env_ids, device=self.device))
         if self._render is not None and self._render.any_armed:     # a reset of the recorded env ends or starts a recording (:1003-1015)
             self._render.note_reset(None if full else env_ids)
+        if self._reward is not None and self._reward.armed:         # the reset cleared histories the reward family keeps a snapshot of
+            self._reward.snapshot()
 
     def set_idx_pose(self, env_ids, dof_pos, base_state):
         """reference legged_robot.py:241-261: the buffers ARE the simulator state, so writing them is the push."""
@@ -809,13 +814,51 @@ class LeggedRobot(BaseTask):
         launch and the device-to-host copies"""
         return self._started("read_trunk_metrics", "_trunk", "start_trunk_metrics").read()
 
+    # ---- the reward term by term (include/go1reward.h, libgo1reward.so: a library of its own): the step kernel adds its reward terms to
+    # episode_sums and stores only the clipped total; while this family is armed one more launch per step, after the trunk family's,
+    # evaluates the terms of the step just taken once more with the step kernel's own device functions and folds them per environment
+    # (K terms, their sum, its positive and negative part, and the clipped total).  The step of a reset and the step of a teleport are
+    # counted, not measured.  Independent of the other measurements.
+    def start_reward_metrics(self, groups, warmup_steps=0):
+        """begin a reward measurement: `groups` = one int per environment (the row of the result tables it counts towards, -1 = not
+        evaluated); steps with episode_length_buf <= warmup_steps fold nothing"""
+        self._need_gpu_metrics("start_reward_metrics")
+        if self._reward is None:
+            import go1reward_host
+            self._reward = go1reward_host.Go1Reward(self.sim_config, self.buffers, self.reward_names)
+        self._reward.arm(groups, warmup_steps)
+
+    def stop_reward_metrics(self):
+        """stop folding steps; what was measured stays readable"""
+        self._disarm("stop_reward_metrics", "_reward")
+
+    def read_reward_metrics(self):
+        """go1reward_host.Go1Reward.read(): {"names", "scales", "terms": {name: (groups, 6)}, "sum", "positive", "negative", "total":
+        (groups, 6), "share": {name: (groups,)}, "groups": (groups, 4) array of envs, measured, reset, teleported env-steps, and the
+        per-environment state}: one reduction launch and the device-to-host copies"""
+        return self._started("read_reward_metrics", "_reward", "start_reward_metrics").read()
+
+    def last_reward_terms(self):
+        """((K + 4, N) scaled terms, sum, positive, negative and total of the last accumulated step, (N,) valid): views, no copy"""
+        return self._started("last_reward_terms", "_reward", "start_reward_metrics").last()
+
+    @property
+    def reward_functions(self):
+        """the reference's list of bound `_reward_*` methods (read by eval_metrics.metrics.auxiliary_rewards).  It exists only while the
+        reward family is armed and has accumulated a step: K callables in reward_names order, each returning the LAST step's raw term
+        (they do not recompute: called twice they return the same).  Otherwise the attribute does not exist: hasattr() is false."""
+        family = self._reward
+        if family is None or not family.armed or family.accumulated == 0:
+            raise AttributeError(f"'{type(self).__name__}' object has no attribute 'reward_functions'")
+        return family.raw_functions()
+
     # ---- the state (include/go1state.h, libgo1state.so: a library of its own): hold a moment still.  save_state() gathers the full
     # simulator state of chosen environments into a packed snapshot on the device (one launch), load_state() scatters snapshot rows
     # into chosen environments (one launch), re-phased to where the lag and history rings stand now.  Neither runs during step(): an
     # environment that never saves imports nothing.  What a snapshot does not hold: the terrain, the configuration, the host-backend
     # curriculum objects (device_curriculum=False), and the accumulators of the measurement families.
     _STATE_FAMILIES = (("metrics", "_metrics"), ("behaviour", "_behaviour"), ("trace", "_trace"), ("terrain", "_traversal"),
-                       ("joints", "_joints"), ("feet", "_feet"), ("trunk", "_trunk"))
+                       ("joints", "_joints"), ("feet", "_feet"), ("trunk", "_trunk"), ("rewards", "_reward"))
 
     def _stater(self, what):
         if self._state is None:

@@ -72,7 +72,8 @@ def adaptation_loss(env, actor_critic, obs):
 def auxiliary_rewards(env, actor_critic, obs):
     """{reward name: scaled reward}.  The reference returns from inside its loop, after the FIRST reward term; kept (SURVEY.md
     App. D: the reference's quirks are reproduced, not repaired), so the dict holds one entry — or the call returns None for an
-    environment without reward terms."""
+    environment without reward terms.  LeggedRobot has `reward_functions` while its reward family is armed and has accumulated a step
+    (`start_reward_metrics`, include/go1reward.h): the callables return the LAST step's raw terms, NaN where that step was not measured."""
     if not hasattr(env, "reward_functions"):
         # LeggedRobot here evaluates the reward terms inside the step kernel: there are no per-term callables to run
         raise NotImplementedError("auxiliary_rewards: this environment has no `reward_functions` (the rewards are computed by the step kernel)")
