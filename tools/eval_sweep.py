@@ -62,6 +62,15 @@ the support polygon, and the lateral drift, heading drift and progress error per
 `--tilt-limit` is the sine beyond which a step counts as tilted too far.  `<out>/eval/<preset>_trunk.json` and the tilt histogram
 `<preset>_tilt.png` are written and the table is printed and appended to `<preset>_trunk.md`.
 
+    python tools/eval_sweep.py --checkpoint RUN_DIR/checkpoints --out RUN_DIR --coordination --vx 1.0 --gaits trotting pacing bounding pronking
+
+With `--coordination` the grid (its `--gaits` axis is what this sweep is for) is swept with the gait table armed beside the scalar one
+(go1_gym_learn.eval_metrics.gait, include/go1gait.h): the synchrony of the pairs of feet, the touchdown phases of FR, RL and RR within
+FL's stride against the commanded ones, the realised gait's class, and the shares of flight, single, pair, three- and four-foot support.
+`--min-stride-steps` debounces FL's touchdowns (default 1: none), `--max-stride-steps` drops longer strides (default 100).
+`<out>/eval/<preset>_gait.json` and the polar figure `<preset>_gait.png` are written and the table is printed and appended to
+`<preset>_gait.md`.
+
     python tools/eval_sweep.py --checkpoint RUN_DIR/checkpoints --out RUN_DIR --rewards --vx 0.5 1.0 1.5
 
 With `--rewards` the velocity grid is swept with the reward table armed beside the scalar one (go1_gym_learn.eval_metrics.rewards,
@@ -161,6 +170,9 @@ def parse_args(argv=None):
     ap.add_argument("--trunk", action="store_true", help="measure trunk motion, support margin and path drift over the velocity grid, beside the scalar table")
     ap.add_argument("--segment-steps", type=int, default=None, help="with --trunk: policy steps of a drift segment, default 50")
     ap.add_argument("--tilt-limit", type=float, default=None, help="with --trunk: the sine of the tilt beyond which a step is counted, default 0.25")
+    ap.add_argument("--coordination", action="store_true", help="measure inter-leg coordination and the realised gait over the grid, beside the scalar table")
+    ap.add_argument("--min-stride-steps", type=int, default=None, help="with --coordination: a touchdown of FL sooner after the last is chatter, default 1")
+    ap.add_argument("--max-stride-steps", type=int, default=None, help="with --coordination: a stride that outgrows it is dropped, default 100")
     ap.add_argument("--rewards", action="store_true", help="break the step reward down by term over the velocity grid, beside the scalar table")
     ap.add_argument("--out", required=True)
     a = ap.parse_args(argv)
@@ -187,6 +199,15 @@ def parse_args(argv=None):
         ap.error("--trunk excludes --terrain (bare), --response, --behaviour, --push, --joints and --feet")
     if a.rewards and (a.tiles or a.response or a.behaviour or a.push or a.joints or a.feet or a.trunk):
         ap.error("--rewards excludes --terrain (bare), --response, --behaviour, --push, --joints, --feet and --trunk")
+    if a.coordination and (a.tiles or a.response or a.behaviour or a.push or a.joints or a.feet or a.trunk or a.rewards):
+        ap.error("--coordination excludes --terrain (bare), --response, --behaviour, --push, --joints, --feet, --trunk and --rewards")
+    if not a.coordination and (a.min_stride_steps is not None or a.max_stride_steps is not None):
+        ap.error("--min-stride-steps and --max-stride-steps need --coordination")
+    if a.coordination:
+        a.min_stride_steps = 1 if a.min_stride_steps is None else a.min_stride_steps
+        a.max_stride_steps = 100 if a.max_stride_steps is None else a.max_stride_steps
+        if a.min_stride_steps < 1 or a.max_stride_steps < a.min_stride_steps:
+            ap.error("--min-stride-steps has to be at least 1 and --max-stride-steps no smaller than it")
     if not a.trunk and (a.segment_steps is not None or a.tilt_limit is not None):
         ap.error("--segment-steps and --tilt-limit need --trunk")
     if a.trunk:
@@ -321,6 +342,21 @@ def run_trunk(a, policy, grid):
         trunk.plot_tilt(res, stem + "_tilt.png")
 
 
+def run_gait(a, policy, grid):
+    from go1_gym_learn.eval_metrics import gait
+    for preset in a.presets:
+        res = gait.run_gait_sweep(policy, preset, grid, num_envs=a.envs, steps=a.steps, warmup_steps=a.warmup_steps, seed=a.seed, terrain=a.terrain,
+                                  min_stride_steps=a.min_stride_steps, max_stride_steps=a.max_stride_steps)
+        stem = os.path.join(a.out, "eval", preset)
+        with open(stem + "_gait.json", "w") as f:
+            json.dump(gait.gait_to_json(res), f, indent=1)
+        text = f"### {preset}: {a.envs} environments, {a.steps} steps, vx {a.vx}, gaits {a.gaits}, inter-leg coordination\n\n" + gait.gait_markdown_table(res) + "\n"
+        print(text)
+        with open(stem + "_gait.md", "a") as f:
+            f.write(text + "\n")
+        gait.plot_gait(res, stem + "_gait.png")
+
+
 def run_rewards(a, policy, grid):
     from go1_gym_learn.eval_metrics import rewards
     for preset in a.presets:
@@ -367,6 +403,8 @@ def main(argv=None):
         return run_feet(a, policy, grid)
     if a.trunk:
         return run_trunk(a, policy, grid)
+    if a.coordination:
+        return run_gait(a, policy, grid)
     if a.rewards:
         return run_rewards(a, policy, grid)
     if a.behaviour:

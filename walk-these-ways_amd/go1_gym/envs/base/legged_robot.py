@@ -155,6 +155,7 @@ class LeggedRobot(BaseTask):
         self._joints = None               # go1eval_host.Go1Joints, created by the first start_joint_metrics()
         self._feet = None                 # go1feet_host.Go1Feet, created by the first start_foot_metrics()
         self._trunk = None                # go1trunk_host.Go1Trunk, created by the first start_trunk_metrics()
+        self._gait = None                 # go1gait_host.Go1Gait, created by the first start_gait_metrics()
         self._reward = None               # go1reward_host.Go1Reward, created by the first start_reward_metrics()
         self._state = None                # go1state_host.Go1State, created by the first save_state() / load_state()
         if eval_cfg is not None:          # reference legged_robot.py:41-42
@@ -461,6 +462,8 @@ class LeggedRobot(BaseTask):
             self._feet.accumulate()
         if self._trunk is not None and self._trunk.armed:
             self._trunk.accumulate()
+        if self._gait is not None and self._gait.armed:
+            self._gait.accumulate()
         if self._reward is not None and self._reward.armed:
             self._reward.accumulate(H.gravity_at(self.sim_config, self.common_step_counter))     # (the gravity of the step just taken)
         if self._curriculum_sync and (self.common_step_counter + 1) % self.sim_config.curriculum_update_interval == 0:
@@ -814,8 +817,33 @@ class LeggedRobot(BaseTask):
         launch and the device-to-host copies"""
         return self._started("read_trunk_metrics", "_trunk", "start_trunk_metrics").read()
 
+    # ---- inter-leg coordination (include/go1gait.h, libgo1gait.so: a library of its own): fifteen values per environment (the synchrony of
+    # the six pairs of feet, and per stride of the reference foot FL the touchdown phases of the other three against the commanded ones and
+    # their touchdown counts), a support-pattern histogram and three touchdown-phase histograms.  One more launch per step while it is
+    # armed, after the trunk family's; independent of the other measurements.
+    def start_gait_metrics(self, groups, warmup_steps=0, min_stride_steps=1, max_stride_steps=100):
+        """begin a gait measurement: `groups` = one int per environment (the row of the result tables it counts towards, -1 = not
+        evaluated); steps with episode_length_buf <= warmup_steps fold nothing and end an open stride.  min_stride_steps: a touchdown
+        of FL sooner after the stride's opening is chatter (1: no debounce); max_stride_steps: a stride that outgrows it is dropped
+        (100 is 2 s)"""
+        self._need_gpu_metrics("start_gait_metrics")
+        if self._gait is None:
+            import go1gait_host
+            self._gait = go1gait_host.Go1Gait(self.sim_config, self.buffers)
+        self._gait.arm(groups, warmup_steps, min_stride_steps=min_stride_steps, max_stride_steps=max_stride_steps)
+
+    def stop_gait_metrics(self):
+        """stop folding steps; what was measured stays readable"""
+        self._disarm("stop_gait_metrics", "_gait")
+
+    def read_gait_metrics(self):
+        """go1gait_host.Go1Gait.read(): {"metrics": {name: (groups, 6)}, "groups": (groups, 5) array of envs, steps, resets, strides,
+        strides_dropped, "support_hist": (groups, 16), "phase_hist": (groups, 3, 16), "phase_centres": (16,), "support_patterns", and the
+        per-environment state}: one reduction launch and the device-to-host copies"""
+        return self._started("read_gait_metrics", "_gait", "start_gait_metrics").read()
+
     # ---- the reward term by term (include/go1reward.h, libgo1reward.so: a library of its own): the step kernel adds its reward terms to
-    # episode_sums and stores only the clipped total; while this family is armed one more launch per step, after the trunk family's,
+    # episode_sums and stores only the clipped total; while this family is armed one more launch per step, after the gait family's,
     # evaluates the terms of the step just taken once more with the step kernel's own device functions and folds them per environment
     # (K terms, their sum, its positive and negative part, and the clipped total).  The step of a reset and the step of a teleport are
     # counted, not measured.  Independent of the other measurements.
@@ -858,7 +886,7 @@ class LeggedRobot(BaseTask):
     # environment that never saves imports nothing.  What a snapshot does not hold: the terrain, the configuration, the host-backend
     # curriculum objects (device_curriculum=False), and the accumulators of the measurement families.
     _STATE_FAMILIES = (("metrics", "_metrics"), ("behaviour", "_behaviour"), ("trace", "_trace"), ("terrain", "_traversal"),
-                       ("joints", "_joints"), ("feet", "_feet"), ("trunk", "_trunk"), ("rewards", "_reward"))
+                       ("joints", "_joints"), ("feet", "_feet"), ("trunk", "_trunk"), ("gait", "_gait"), ("rewards", "_reward"))
 
     def _stater(self, what):
         if self._state is None:
