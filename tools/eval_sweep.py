@@ -71,6 +71,15 @@ FL's stride against the commanded ones, the realised gait's class, and the share
 `<out>/eval/<preset>_gait.json` and the polar figure `<preset>_gait.png` are written and the table is printed and appended to
 `<preset>_gait.md`.
 
+    python tools/eval_sweep.py --checkpoint RUN_DIR/checkpoints --out RUN_DIR --spectrum --vx 0.5 1.0 1.5
+
+With `--spectrum` the velocity grid is swept with the spectral table armed beside the scalar one (go1_gym_learn.eval_metrics.spectrum,
+include/go1spectrum.h): the power spectral density of the actions, torques, joint speeds and trunk rates over segments of
+`--segment-steps` steps (even, 8 to 128, default 100), and per quantity and joint type the rms, the dominant frequency and its share,
+the share at and above `--high-freq` (default 10 Hz, a placeholder), the centroid and the share locked to the harmonics of the
+commanded step frequency; `--taper` is hann (default) or boxcar.  `<out>/eval/<preset>_spectrum.json` and the figure
+`<preset>_spectrum.png` are written and the table is printed and appended to `<preset>_spectrum.md`.
+
     python tools/eval_sweep.py --checkpoint RUN_DIR/checkpoints --out RUN_DIR --rewards --vx 0.5 1.0 1.5
 
 With `--rewards` the velocity grid is swept with the reward table armed beside the scalar one (go1_gym_learn.eval_metrics.rewards,
@@ -168,11 +177,14 @@ def parse_args(argv=None):
     ap.add_argument("--joints", action="store_true", help="measure per-joint actuator usage over the velocity grid, beside the scalar table")
     ap.add_argument("--feet", action="store_true", help="measure per-foot ground reaction forces over the velocity grid, beside the scalar table")
     ap.add_argument("--trunk", action="store_true", help="measure trunk motion, support margin and path drift over the velocity grid, beside the scalar table")
-    ap.add_argument("--segment-steps", type=int, default=None, help="with --trunk: policy steps of a drift segment, default 50")
+    ap.add_argument("--segment-steps", type=int, default=None, help="with --trunk: policy steps of a drift segment, default 50; with --spectrum: of a transformed segment, default 100")
     ap.add_argument("--tilt-limit", type=float, default=None, help="with --trunk: the sine of the tilt beyond which a step is counted, default 0.25")
     ap.add_argument("--coordination", action="store_true", help="measure inter-leg coordination and the realised gait over the grid, beside the scalar table")
     ap.add_argument("--min-stride-steps", type=int, default=None, help="with --coordination: a touchdown of FL sooner after the last is chatter, default 1")
     ap.add_argument("--max-stride-steps", type=int, default=None, help="with --coordination: a stride that outgrows it is dropped, default 100")
+    ap.add_argument("--spectrum", action="store_true", help="measure action, torque, joint-speed and trunk-rate spectra over the velocity grid, beside the scalar table")
+    ap.add_argument("--high-freq", type=float, default=None, help="with --spectrum: high_share counts the bins from this frequency on, default 10 Hz")
+    ap.add_argument("--taper", default=None, choices=["hann", "boxcar"], help="with --spectrum: the taper of a segment, default hann")
     ap.add_argument("--rewards", action="store_true", help="break the step reward down by term over the velocity grid, beside the scalar table")
     ap.add_argument("--out", required=True)
     a = ap.parse_args(argv)
@@ -208,8 +220,22 @@ def parse_args(argv=None):
         a.max_stride_steps = 100 if a.max_stride_steps is None else a.max_stride_steps
         if a.min_stride_steps < 1 or a.max_stride_steps < a.min_stride_steps:
             ap.error("--min-stride-steps has to be at least 1 and --max-stride-steps no smaller than it")
-    if not a.trunk and (a.segment_steps is not None or a.tilt_limit is not None):
-        ap.error("--segment-steps and --tilt-limit need --trunk")
+    if a.spectrum and (a.tiles or a.response or a.behaviour or a.push or a.joints or a.feet or a.trunk or a.rewards or a.coordination):
+        ap.error("--spectrum excludes --terrain (bare), --response, --behaviour, --push, --joints, --feet, --trunk, --rewards and --coordination")
+    if not a.spectrum and (a.high_freq is not None or a.taper is not None):
+        ap.error("--high-freq and --taper need --spectrum")
+    if a.spectrum:
+        a.segment_steps = 100 if a.segment_steps is None else a.segment_steps
+        a.high_freq = 10.0 if a.high_freq is None else a.high_freq
+        a.taper = a.taper or "hann"
+        if a.segment_steps % 2 or not 8 <= a.segment_steps <= 128:
+            ap.error("--segment-steps has to be even and in [8, 128] with --spectrum")
+        if not 0.0 < a.high_freq < float("inf"):
+            ap.error("--high-freq has to be a positive frequency")
+    if not (a.trunk or a.spectrum) and (a.segment_steps is not None or a.tilt_limit is not None):
+        ap.error("--segment-steps and --tilt-limit need --trunk (--segment-steps alone: or --spectrum)")
+    if a.spectrum and a.tilt_limit is not None:
+        ap.error("--tilt-limit needs --trunk")
     if a.trunk:
         a.segment_steps = 50 if a.segment_steps is None else a.segment_steps
         a.tilt_limit = 0.25 if a.tilt_limit is None else a.tilt_limit
@@ -357,6 +383,22 @@ def run_gait(a, policy, grid):
         gait.plot_gait(res, stem + "_gait.png")
 
 
+def run_spectrum(a, policy, grid):
+    from go1_gym_learn.eval_metrics import spectrum
+    for preset in a.presets:
+        res = spectrum.run_spectrum_sweep(policy, preset, grid, num_envs=a.envs, steps=a.steps, warmup_steps=a.warmup_steps, seed=a.seed, terrain=a.terrain,
+                                          segment_steps=a.segment_steps, high_freq=a.high_freq, taper=a.taper)
+        stem = os.path.join(a.out, "eval", preset)
+        with open(stem + "_spectrum.json", "w") as f:
+            json.dump(spectrum.spectrum_to_json(res), f, indent=1)
+        text = (f"### {preset}: {a.envs} environments, {a.steps} steps, vx {a.vx}, spectra over {a.segment_steps}-step segments ({a.taper})\n\n" +
+                spectrum.spectrum_markdown_table(res) + "\n")
+        print(text)
+        with open(stem + "_spectrum.md", "a") as f:
+            f.write(text + "\n")
+        spectrum.plot_spectrum(res, stem + "_spectrum.png")
+
+
 def run_rewards(a, policy, grid):
     from go1_gym_learn.eval_metrics import rewards
     for preset in a.presets:
@@ -405,6 +447,8 @@ def main(argv=None):
         return run_trunk(a, policy, grid)
     if a.coordination:
         return run_gait(a, policy, grid)
+    if a.spectrum:
+        return run_spectrum(a, policy, grid)
     if a.rewards:
         return run_rewards(a, policy, grid)
     if a.behaviour:

@@ -156,6 +156,7 @@ class LeggedRobot(BaseTask):
         self._feet = None                 # go1feet_host.Go1Feet, created by the first start_foot_metrics()
         self._trunk = None                # go1trunk_host.Go1Trunk, created by the first start_trunk_metrics()
         self._gait = None                 # go1gait_host.Go1Gait, created by the first start_gait_metrics()
+        self._spectrum = None             # go1spectrum_host.Go1Spectrum, created by the first start_spectrum_metrics()
         self._reward = None               # go1reward_host.Go1Reward, created by the first start_reward_metrics()
         self._state = None                # go1state_host.Go1State, created by the first save_state() / load_state()
         if eval_cfg is not None:          # reference legged_robot.py:41-42
@@ -464,6 +465,8 @@ class LeggedRobot(BaseTask):
             self._trunk.accumulate()
         if self._gait is not None and self._gait.armed:
             self._gait.accumulate()
+        if self._spectrum is not None and self._spectrum.armed:
+            self._spectrum.accumulate()
         if self._reward is not None and self._reward.armed:
             self._reward.accumulate(H.gravity_at(self.sim_config, self.common_step_counter))     # (the gravity of the step just taken)
         if self._curriculum_sync and (self.common_step_counter + 1) % self.sim_config.curriculum_update_interval == 0:
@@ -842,8 +845,33 @@ class LeggedRobot(BaseTask):
         per-environment state}: one reduction launch and the device-to-host copies"""
         return self._started("read_gait_metrics", "_gait", "start_gait_metrics").read()
 
+    # ---- spectra (include/go1spectrum.h, libgo1spectrum.so: a library of its own): the power spectral density of forty signals (the
+    # twelve clipped actions, torques and joint speeds, the three trunk rates and the vertical velocity) by Welch's method over segments
+    # of the family's own step clock, and per closed segment five band figures per signal.  One more launch per step while it is armed,
+    # after the gait family's, and one fold launch per segment_steps steps; independent of the other measurements.
+    def start_spectrum_metrics(self, groups, warmup_steps=0, segment_steps=100, high_freq=10.0, taper="hann"):
+        """begin a spectral measurement: `groups` = one int per environment (the row of the result tables it counts towards, -1 = not
+        evaluated); a step with episode_length_buf <= warmup_steps or a reset spoils the segment it falls in.  segment_steps: even, 8 to
+        128 policy steps per segment (100 is 2 s: 0.5 Hz bins up to 25 Hz); high_freq: high_share counts the bins from this frequency on
+        (10 Hz is a placeholder, nothing measured stands behind it); taper: "hann" or "boxcar" """
+        self._need_gpu_metrics("start_spectrum_metrics")
+        if self._spectrum is None:
+            import go1spectrum_host
+            self._spectrum = go1spectrum_host.Go1Spectrum(self.sim_config, self.buffers, self.dt)
+        self._spectrum.arm(groups, warmup_steps, segment_steps=segment_steps, high_freq=high_freq, taper=taper)
+
+    def stop_spectrum_metrics(self):
+        """stop recording steps; what was measured stays readable.  A segment left open is discarded, not counted as dropped"""
+        self._disarm("stop_spectrum_metrics", "_spectrum")
+
+    def read_spectrum_metrics(self):
+        """go1spectrum_host.Go1Spectrum.read(): {"metrics": {row: (groups, 40, 6)}, "groups": (groups, 5) array of envs, steps, resets,
+        segments, segments_dropped, "psd": (groups, 40, F) mean density, "psd_segments": (groups, 40), "freq": (F,), "signals": the forty
+        names, "high_bin", and the per-environment state}: one reduction launch and the device-to-host copies"""
+        return self._started("read_spectrum_metrics", "_spectrum", "start_spectrum_metrics").read()
+
     # ---- the reward term by term (include/go1reward.h, libgo1reward.so: a library of its own): the step kernel adds its reward terms to
-    # episode_sums and stores only the clipped total; while this family is armed one more launch per step, after the gait family's,
+    # episode_sums and stores only the clipped total; while this family is armed one more launch per step, after the spectrum family's,
     # evaluates the terms of the step just taken once more with the step kernel's own device functions and folds them per environment
     # (K terms, their sum, its positive and negative part, and the clipped total).  The step of a reset and the step of a teleport are
     # counted, not measured.  Independent of the other measurements.
@@ -886,7 +914,8 @@ class LeggedRobot(BaseTask):
     # environment that never saves imports nothing.  What a snapshot does not hold: the terrain, the configuration, the host-backend
     # curriculum objects (device_curriculum=False), and the accumulators of the measurement families.
     _STATE_FAMILIES = (("metrics", "_metrics"), ("behaviour", "_behaviour"), ("trace", "_trace"), ("terrain", "_traversal"),
-                       ("joints", "_joints"), ("feet", "_feet"), ("trunk", "_trunk"), ("gait", "_gait"), ("rewards", "_reward"))
+                       ("joints", "_joints"), ("feet", "_feet"), ("trunk", "_trunk"), ("gait", "_gait"), ("spectrum", "_spectrum"),
+                       ("rewards", "_reward"))
 
     def _stater(self, what):
         if self._state is None:

@@ -7,4 +7,5 @@ which tiles of a generated terrain a policy crosses, and how (`run_terrain_sweep
 (`joint_terms`, `run_joint_sweep`, `plot_envelope`), `feet` what every foot puts into the ground (`foot_terms`, `run_foot_sweep`, `plot_grf`;
 include/go1feet.h), `trunk` what the trunk does: tilt, accelerations, support margin and path drift (`trunk_terms`, `run_trunk_sweep`,
 `plot_tilt`; include/go1trunk.h), `gait` how the legs move relative to one another and which gait that is (`run_gait_sweep`, `classify`,
-`plot_gait`; include/go1gait.h)."""
+`plot_gait`; include/go1gait.h), `spectrum` where in frequency the actions, torques, joint speeds and trunk rates carry their energy
+(`run_spectrum_sweep`, `gait_locked`, `plot_spectrum`; include/go1spectrum.h)."""
