@@ -86,6 +86,15 @@ With `--rewards` the velocity grid is swept with the reward table armed beside t
 include/go1reward.h): the mean scaled reward per step of every active term and its share, their sum, its positive and negative part,
 the total after the clip and what the clip forgave, per cell.  `<out>/eval/<preset>_rewards.json` and the stacked-bar figure
 `<preset>_rewards.png` are written and the table is printed and appended to `<preset>_rewards.md`.
+
+    python tools/eval_sweep.py --checkpoint RUN_DIR/checkpoints --out RUN_DIR --placement --axis stance_width 0.1 0.3 0.45
+
+With `--placement` the product of the `--axis NAME V1 V2 ...` command values (as with `--behaviour`: stance_width, stance_length, vx,
+frequency, ...) is swept with the placement table armed beside the scalar one (go1_gym_learn.eval_metrics.placement,
+include/go1place.h): per foot where it touches down against its nominal stance point and against the Raibert heuristic's target, the
+mean error in stance and in swing, the stance sweep, the stride length against |v| / f, the track width against the commanded one, and
+an 8 x 8 footprint map of `--map-cell` metres per cell (default 0.03, a placeholder).  `<out>/eval/<preset>_placement.json` and the
+footprint figure `<preset>_footprints.png` are written and the table is printed and appended to `<preset>_placement.md`.
 Run on the GPU box."""
 import argparse
 import json
@@ -186,6 +195,8 @@ def parse_args(argv=None):
     ap.add_argument("--high-freq", type=float, default=None, help="with --spectrum: high_share counts the bins from this frequency on, default 10 Hz")
     ap.add_argument("--taper", default=None, choices=["hann", "boxcar"], help="with --spectrum: the taper of a segment, default hann")
     ap.add_argument("--rewards", action="store_true", help="break the step reward down by term over the velocity grid, beside the scalar table")
+    ap.add_argument("--placement", action="store_true", help="measure foot placement and stride geometry over the --axis product, beside the scalar table")
+    ap.add_argument("--map-cell", type=float, default=None, help="with --placement: the side of a cell of the footprint map in metres, default 0.03")
     ap.add_argument("--out", required=True)
     a = ap.parse_args(argv)
     a.tiles = a.terrain == "tiles"
@@ -232,6 +243,14 @@ def parse_args(argv=None):
             ap.error("--segment-steps has to be even and in [8, 128] with --spectrum")
         if not 0.0 < a.high_freq < float("inf"):
             ap.error("--high-freq has to be a positive frequency")
+    if a.placement and (a.tiles or a.response or a.behaviour or a.push or a.joints or a.feet or a.trunk or a.rewards or a.coordination or a.spectrum):
+        ap.error("--placement excludes --terrain (bare), --response, --behaviour, --push, --joints, --feet, --trunk, --rewards, --coordination and --spectrum")
+    if not a.placement and a.map_cell is not None:
+        ap.error("--map-cell needs --placement")
+    if a.placement:
+        a.map_cell = 0.03 if a.map_cell is None else a.map_cell
+        if not 0.0 < a.map_cell < float("inf"):
+            ap.error("--map-cell has to be a positive length")
     if not (a.trunk or a.spectrum) and (a.segment_steps is not None or a.tilt_limit is not None):
         ap.error("--segment-steps and --tilt-limit need --trunk (--segment-steps alone: or --spectrum)")
     if a.spectrum and a.tilt_limit is not None:
@@ -413,11 +432,26 @@ def run_rewards(a, policy, grid):
         rewards.plot_reward_shares(res, stem + "_rewards.png")
 
 
+def run_placement(a, policy, axes):
+    from go1_gym_learn.eval_metrics import placement
+    for preset in a.presets:
+        res = placement.run_placement_sweep(policy, preset, axes, num_envs=a.envs, steps=a.steps, warmup_steps=a.warmup_steps, seed=a.seed, terrain=a.terrain,
+                                            map_cell=a.map_cell)
+        stem = os.path.join(a.out, "eval", preset)
+        with open(stem + "_placement.json", "w") as f:
+            json.dump(placement.placement_to_json(res), f, indent=1)
+        text = f"### {preset}: {a.envs} environments, {a.steps} steps, axes {axes}, foot placement\n\n" + placement.placement_table(res) + "\n"
+        print(text)
+        with open(stem + "_placement.md", "a") as f:
+            f.write(text + "\n")
+        placement.plot_footprints(res, stem + "_footprints.png")
+
+
 def behaviour_axes(a):
     """{command name: [values]} of the --axis options, in the order given"""
     from go1_gym_learn.eval_metrics.behaviour import COMMAND_INDEX
     if not a.axis:
-        raise SystemExit("--behaviour needs at least one --axis NAME V1 V2 ...")
+        raise SystemExit(("--placement" if a.placement else "--behaviour") + " needs at least one --axis NAME V1 V2 ...")
     axes = {}
     for name, *values in a.axis:
         if name not in COMMAND_INDEX or not values:
@@ -451,6 +485,8 @@ def main(argv=None):
         return run_spectrum(a, policy, grid)
     if a.rewards:
         return run_rewards(a, policy, grid)
+    if a.placement:
+        return run_placement(a, policy, behaviour_axes(a))
     if a.behaviour:
         from go1_gym_learn.eval_metrics import behaviour
         axes = behaviour_axes(a)

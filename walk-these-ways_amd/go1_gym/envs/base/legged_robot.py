@@ -157,6 +157,7 @@ class LeggedRobot(BaseTask):
         self._trunk = None                # go1trunk_host.Go1Trunk, created by the first start_trunk_metrics()
         self._gait = None                 # go1gait_host.Go1Gait, created by the first start_gait_metrics()
         self._spectrum = None             # go1spectrum_host.Go1Spectrum, created by the first start_spectrum_metrics()
+        self._place = None                # go1place_host.Go1Place, created by the first start_placement_metrics()
         self._reward = None               # go1reward_host.Go1Reward, created by the first start_reward_metrics()
         self._state = None                # go1state_host.Go1State, created by the first save_state() / load_state()
         if eval_cfg is not None:          # reference legged_robot.py:41-42
@@ -467,6 +468,8 @@ class LeggedRobot(BaseTask):
             self._gait.accumulate()
         if self._spectrum is not None and self._spectrum.armed:
             self._spectrum.accumulate()
+        if self._place is not None and self._place.armed:
+            self._place.accumulate()
         if self._reward is not None and self._reward.armed:
             self._reward.accumulate(H.gravity_at(self.sim_config, self.common_step_counter))     # (the gravity of the step just taken)
         if self._curriculum_sync and (self.common_step_counter + 1) % self.sim_config.curriculum_update_interval == 0:
@@ -870,8 +873,32 @@ class LeggedRobot(BaseTask):
         names, "high_bin", and the per-environment state}: one reduction launch and the device-to-host copies"""
         return self._started("read_spectrum_metrics", "_spectrum", "start_spectrum_metrics").read()
 
+    # ---- foot placement (include/go1place.h, libgo1place.so: a library of its own): fourteen values per foot (the error against the Raibert
+    # heuristic's target in stance and in swing, the touchdown and liftoff points against the nominal stance point, the stance sweep, the
+    # stride length and its error, the track width error) and an 8 x 8 footprint map per foot.  One more launch per step while it is
+    # armed, after the spectrum family's; independent of the other measurements.
+    def start_placement_metrics(self, groups, warmup_steps=0, map_cell=0.03):
+        """begin a foot-placement measurement: `groups` = one int per environment (the row of the result tables it counts towards, -1 = not
+        evaluated); steps with episode_length_buf <= warmup_steps fold nothing and end every open stance and stride.  map_cell: the side
+        of a cell of the footprint map in metres (0.03 is a placeholder, nothing measured stands behind it: the map spans +-0.12 m)"""
+        self._need_gpu_metrics("start_placement_metrics")
+        if self._place is None:
+            import go1place_host
+            self._place = go1place_host.Go1Place(self.sim_config, self.buffers)
+        self._place.arm(groups, warmup_steps, map_cell=map_cell)
+
+    def stop_placement_metrics(self):
+        """stop folding steps; what was measured stays readable"""
+        self._disarm("stop_placement_metrics", "_place")
+
+    def read_placement_metrics(self):
+        """go1place_host.Go1Place.read(): {"metrics": {name: (groups, 4, 6)}, "groups": (groups, 6) array of envs, steps, resets, touchdowns,
+        strides, map_outside, "map": (groups, 4, 8, 8), "map_edges": (9,), and the per-environment state}: one reduction launch and the
+        device-to-host copies"""
+        return self._started("read_placement_metrics", "_place", "start_placement_metrics").read()
+
     # ---- the reward term by term (include/go1reward.h, libgo1reward.so: a library of its own): the step kernel adds its reward terms to
-    # episode_sums and stores only the clipped total; while this family is armed one more launch per step, after the spectrum family's,
+    # episode_sums and stores only the clipped total; while this family is armed one more launch per step, after the placement family's,
     # evaluates the terms of the step just taken once more with the step kernel's own device functions and folds them per environment
     # (K terms, their sum, its positive and negative part, and the clipped total).  The step of a reset and the step of a teleport are
     # counted, not measured.  Independent of the other measurements.
@@ -915,7 +942,7 @@ class LeggedRobot(BaseTask):
     # curriculum objects (device_curriculum=False), and the accumulators of the measurement families.
     _STATE_FAMILIES = (("metrics", "_metrics"), ("behaviour", "_behaviour"), ("trace", "_trace"), ("terrain", "_traversal"),
                        ("joints", "_joints"), ("feet", "_feet"), ("trunk", "_trunk"), ("gait", "_gait"), ("spectrum", "_spectrum"),
-                       ("rewards", "_reward"))
+                       ("placement", "_place"), ("rewards", "_reward"))
 
     def _stater(self, what):
         if self._state is None:

@@ -8,4 +8,6 @@ which tiles of a generated terrain a policy crosses, and how (`run_terrain_sweep
 include/go1feet.h), `trunk` what the trunk does: tilt, accelerations, support margin and path drift (`trunk_terms`, `run_trunk_sweep`,
 `plot_tilt`; include/go1trunk.h), `gait` how the legs move relative to one another and which gait that is (`run_gait_sweep`, `classify`,
 `plot_gait`; include/go1gait.h), `spectrum` where in frequency the actions, torques, joint speeds and trunk rates carry their energy
-(`run_spectrum_sweep`, `gait_locked`, `plot_spectrum`; include/go1spectrum.h)."""
+(`run_spectrum_sweep`, `gait_locked`, `plot_spectrum`; include/go1spectrum.h), `placement` where every foot lands against its nominal stance
+point and the Raibert heuristic's target, and the stride length and track width the robot realises (`placement_errors`, `run_placement_sweep`,
+`plot_footprints`; include/go1place.h)."""
