@@ -97,9 +97,11 @@ an 8 x 8 footprint map of `--map-cell` metres per cell (default 0.03, a placehol
 footprint figure `<preset>_footprints.png` are written and the table is printed and appended to `<preset>_placement.md`.
 Run on the GPU box."""
 import argparse
+import functools
 import json
 import os
 import sys
+from typing import Callable, NamedTuple
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(REPO, "walk-these-ways_amd")
@@ -144,11 +146,62 @@ def load_policy(checkpoint_dir, device):
 
 
 def to_json(result):
+    from go1_gym_learn.eval_metrics import sweep
     return dict(preset=result["preset"], num_envs=result["num_envs"], steps=result["steps"], warmup_steps=result["warmup_steps"],
-                seed=result["seed"], cells=[dict(vx=c[0], yaw=c[1], gait=list(c[2])) for c in result["cells"]],
-                fields=["count", "mean", "std", "min", "max", "nonfinite"],
+                seed=result["seed"], cells=sweep.cells_to_json(result["cells"]), fields=list(sweep.FIELDS),
                 metrics={k: v.tolist() for k, v in result["metrics"].items()},
                 group_fields=["envs", "steps", "episodes_terminated", "episodes_timed_out", "fall_rate"], groups=result["groups"].tolist())
+
+
+class Mode(NamedTuple):
+    """a sweep that arms one family's table beside the scalar one: where its functions are, what it writes and what it takes"""
+    flag: str                      # the option that chooses it
+    module: str                    # of go1_gym_learn.eval_metrics, and in it the names of
+    sweep: str                     # the sweep: (policy, preset, grid, num_envs=, steps=, warmup_steps=, seed=, terrain=, **options) -> result
+    to_json: str                   # result -> what <preset><suffix>.json holds
+    table: str                     # result -> the Markdown table printed and appended to <preset><suffix>.md
+    figure: str                    # (result, path) -> the figure <preset><figure_suffix>
+    suffix: str
+    figure_suffix: str
+    headline: str                  # the end of the table's headline, formatted with a = the arguments and grid
+    options: dict = {}             # the mode's own options: name in the arguments -> default
+    check: Callable = lambda a: None                  # the arguments with the defaults in -> what is wrong with the options, if anything
+    figure_input: Callable = lambda res: (res, {})    # result -> what the figure function takes before the path, and its keywords
+    axes: bool = False             # swept over the --axis product instead of the velocity grid
+
+    @property
+    def dest(self):
+        return self.flag[2:]
+
+
+def _joint_envelope(res):
+    return res["hist"], dict(torque_limit=res["torque_limit"][0], vel_limit=res["vel_limit"][:3], soft_torque_limit=res["soft_torque_limit"],
+                             soft_vel_limit=res["soft_vel_limit"])
+
+
+MODES = (
+    Mode("--joints", "joints", "run_joint_sweep", "joint_to_json", "joint_markdown_table", "plot_envelope", "_joints", "_envelope.png",
+         "vx {a.vx}, per-joint actuator usage", figure_input=_joint_envelope),
+    Mode("--feet", "feet", "run_foot_sweep", "foot_to_json", "foot_markdown_table", "plot_grf", "_feet", "_grf.png", "vx {a.vx}, foot loading"),
+    Mode("--trunk", "trunk", "run_trunk_sweep", "trunk_to_json", "trunk_markdown_table", "plot_tilt", "_trunk", "_tilt.png", "vx {a.vx}, trunk motion",
+         options=dict(segment_steps=50, tilt_limit=0.25),
+         check=lambda a: (a.segment_steps < 1 or not 0.0 <= a.tilt_limit < float("inf")) and
+         "--segment-steps has to be at least 1 and --tilt-limit a finite sine that is not negative"),
+    Mode("--rewards", "rewards", "run_reward_sweep", "reward_to_json", "reward_table", "plot_reward_shares", "_rewards", "_rewards.png",
+         "vx {a.vx}, reward by term (mean per step, share)"),
+    Mode("--coordination", "gait", "run_gait_sweep", "gait_to_json", "gait_markdown_table", "plot_gait", "_gait", "_gait.png",
+         "vx {a.vx}, gaits {a.gaits}, inter-leg coordination", options=dict(min_stride_steps=1, max_stride_steps=100),
+         check=lambda a: (a.min_stride_steps < 1 or a.max_stride_steps < a.min_stride_steps) and
+         "--min-stride-steps has to be at least 1 and --max-stride-steps no smaller than it"),
+    Mode("--spectrum", "spectrum", "run_spectrum_sweep", "spectrum_to_json", "spectrum_markdown_table", "plot_spectrum", "_spectrum", "_spectrum.png",
+         "vx {a.vx}, spectra over {a.segment_steps}-step segments ({a.taper})", options=dict(segment_steps=100, high_freq=10.0, taper="hann"),
+         check=lambda a: ((a.segment_steps % 2 or not 8 <= a.segment_steps <= 128) and "--segment-steps has to be even and in [8, 128] with --spectrum") or
+         (not 0.0 < a.high_freq < float("inf") and "--high-freq has to be a positive frequency")),
+    Mode("--placement", "placement", "run_placement_sweep", "placement_to_json", "placement_table", "plot_footprints", "_placement", "_footprints.png",
+         "axes {grid}, foot placement", options=dict(map_cell=0.03), axes=True,
+         check=lambda a: not 0.0 < a.map_cell < float("inf") and "--map-cell has to be a positive length"),
+)
+MODE = {mode.dest: mode for mode in MODES}
 
 
 def parse_args(argv=None):
@@ -202,9 +255,12 @@ def parse_args(argv=None):
     a.tiles = a.terrain == "tiles"
     if not a.tiles and any(v is not None for v in (a.rows, a.cols, a.window, a.mesh, a.proportions)):
         ap.error("--rows, --cols, --window, --mesh and --proportions need a bare --terrain")
+    # one mode per run: every pair of modes excludes each other, except that --response is accepted with --behaviour (the response runs)
+    flags = [("--terrain (bare)", "tiles"), ("--response", "response"), ("--behaviour", "behaviour"), ("--push", "push")] + [(m.flag, m.dest) for m in MODES]
+    chosen = [flag for flag, dest in flags if getattr(a, dest)]
+    if len(chosen) > 1 and chosen != ["--response", "--behaviour"]:
+        ap.error(f"{chosen[0]} excludes {chosen[1]}")
     if a.tiles:
-        if a.response or a.behaviour or a.push:
-            ap.error("a bare --terrain excludes --response, --behaviour and --push")
         if a.vx is not None and len(a.vx) != 1:
             ap.error("a bare --terrain takes one --vx")
         a.terrain = None
@@ -214,52 +270,22 @@ def parse_args(argv=None):
         if a.rows < 1 or a.cols < 1 or a.window < 1:
             ap.error("--rows, --cols and --window have to be at least 1")
     a.vx = a.vx or [0.5, 1.0, 1.5]
-    if a.joints and (a.tiles or a.response or a.behaviour or a.push):
-        ap.error("--joints excludes --terrain (bare), --response, --behaviour and --push")
-    if a.feet and (a.tiles or a.response or a.behaviour or a.push or a.joints):
-        ap.error("--feet excludes --terrain (bare), --response, --behaviour, --push and --joints")
-    if a.trunk and (a.tiles or a.response or a.behaviour or a.push or a.joints or a.feet):
-        ap.error("--trunk excludes --terrain (bare), --response, --behaviour, --push, --joints and --feet")
-    if a.rewards and (a.tiles or a.response or a.behaviour or a.push or a.joints or a.feet or a.trunk):
-        ap.error("--rewards excludes --terrain (bare), --response, --behaviour, --push, --joints, --feet and --trunk")
-    if a.coordination and (a.tiles or a.response or a.behaviour or a.push or a.joints or a.feet or a.trunk or a.rewards):
-        ap.error("--coordination excludes --terrain (bare), --response, --behaviour, --push, --joints, --feet, --trunk and --rewards")
-    if not a.coordination and (a.min_stride_steps is not None or a.max_stride_steps is not None):
-        ap.error("--min-stride-steps and --max-stride-steps need --coordination")
-    if a.coordination:
-        a.min_stride_steps = 1 if a.min_stride_steps is None else a.min_stride_steps
-        a.max_stride_steps = 100 if a.max_stride_steps is None else a.max_stride_steps
-        if a.min_stride_steps < 1 or a.max_stride_steps < a.min_stride_steps:
-            ap.error("--min-stride-steps has to be at least 1 and --max-stride-steps no smaller than it")
-    if a.spectrum and (a.tiles or a.response or a.behaviour or a.push or a.joints or a.feet or a.trunk or a.rewards or a.coordination):
-        ap.error("--spectrum excludes --terrain (bare), --response, --behaviour, --push, --joints, --feet, --trunk, --rewards and --coordination")
-    if not a.spectrum and (a.high_freq is not None or a.taper is not None):
-        ap.error("--high-freq and --taper need --spectrum")
-    if a.spectrum:
-        a.segment_steps = 100 if a.segment_steps is None else a.segment_steps
-        a.high_freq = 10.0 if a.high_freq is None else a.high_freq
-        a.taper = a.taper or "hann"
-        if a.segment_steps % 2 or not 8 <= a.segment_steps <= 128:
-            ap.error("--segment-steps has to be even and in [8, 128] with --spectrum")
-        if not 0.0 < a.high_freq < float("inf"):
-            ap.error("--high-freq has to be a positive frequency")
-    if a.placement and (a.tiles or a.response or a.behaviour or a.push or a.joints or a.feet or a.trunk or a.rewards or a.coordination or a.spectrum):
-        ap.error("--placement excludes --terrain (bare), --response, --behaviour, --push, --joints, --feet, --trunk, --rewards, --coordination and --spectrum")
-    if not a.placement and a.map_cell is not None:
-        ap.error("--map-cell needs --placement")
-    if a.placement:
-        a.map_cell = 0.03 if a.map_cell is None else a.map_cell
-        if not 0.0 < a.map_cell < float("inf"):
-            ap.error("--map-cell has to be a positive length")
-    if not (a.trunk or a.spectrum) and (a.segment_steps is not None or a.tilt_limit is not None):
-        ap.error("--segment-steps and --tilt-limit need --trunk (--segment-steps alone: or --spectrum)")
-    if a.spectrum and a.tilt_limit is not None:
-        ap.error("--tilt-limit needs --trunk")
-    if a.trunk:
-        a.segment_steps = 50 if a.segment_steps is None else a.segment_steps
-        a.tilt_limit = 0.25 if a.tilt_limit is None else a.tilt_limit
-        if a.segment_steps < 1 or not 0.0 <= a.tilt_limit < float("inf"):
-            ap.error("--segment-steps has to be at least 1 and --tilt-limit a finite sine that is not negative")
+    # a mode's own option needs that mode (--segment-steps: either of the two that have one); the chosen mode's options get its defaults
+    owners = {}
+    for mode in MODES:
+        for option in mode.options:
+            owners.setdefault(option, []).append(mode)
+    for option, modes in owners.items():
+        if getattr(a, option) is not None and not any(getattr(a, m.dest) for m in modes):
+            ap.error(f"--{option.replace('_', '-')} needs " + " or ".join(m.flag for m in modes))
+    for mode in MODES:
+        if getattr(a, mode.dest):
+            for option, default in mode.options.items():
+                if getattr(a, option) is None:
+                    setattr(a, option, default)
+            problem = mode.check(a)
+            if problem:
+                ap.error(problem)
     if a.switch and not a.response:
         ap.error("--switch needs --response")
     if a.trace_envs and not (a.response or a.push):
@@ -268,8 +294,6 @@ def parse_args(argv=None):
         ap.error("--magnitude and --direction need --push")
     if a.paired and not a.push:
         ap.error("--paired needs --push")
-    if a.push and (a.response or a.behaviour):
-        ap.error("--push excludes --response and --behaviour")
     if a.push and not (a.magnitude and a.direction):
         ap.error("--push needs --magnitude M [M ...] and --direction D [D ...]")
     if a.push and any(m < 0 for m in a.magnitude):
@@ -343,108 +367,32 @@ def run_terrain(a, policy):
             f.write(text + "\n")
 
 
-def run_joints(a, policy, grid):
-    from go1_gym_learn.eval_metrics import joints
+def run_mode(mode, a, policy, grid):
+    """the sweep of one row of MODES for every preset: <preset><suffix>.json, the headline and the table printed and appended to
+    <preset><suffix>.md, and the figure.  The module's functions are looked up by name when they are called."""
+    import importlib
+    module = importlib.import_module("go1_gym_learn.eval_metrics." + mode.module)
     for preset in a.presets:
-        res = joints.run_joint_sweep(policy, preset, grid, num_envs=a.envs, steps=a.steps, warmup_steps=a.warmup_steps, seed=a.seed, terrain=a.terrain)
+        res = getattr(module, mode.sweep)(policy, preset, grid, num_envs=a.envs, steps=a.steps, warmup_steps=a.warmup_steps, seed=a.seed, terrain=a.terrain,
+                                          **{option: getattr(a, option) for option in mode.options})
         stem = os.path.join(a.out, "eval", preset)
-        with open(stem + "_joints.json", "w") as f:
-            json.dump(joints.joint_to_json(res), f, indent=1)
-        text = f"### {preset}: {a.envs} environments, {a.steps} steps, vx {a.vx}, per-joint actuator usage\n\n" + joints.joint_markdown_table(res) + "\n"
+        with open(stem + mode.suffix + ".json", "w") as f:
+            json.dump(getattr(module, mode.to_json)(res), f, indent=1)
+        text = f"### {preset}: {a.envs} environments, {a.steps} steps, " + mode.headline.format(a=a, grid=grid) + "\n\n" + getattr(module, mode.table)(res) + "\n"
         print(text)
-        with open(stem + "_joints.md", "a") as f:
+        with open(stem + mode.suffix + ".md", "a") as f:
             f.write(text + "\n")
-        joints.plot_envelope(res["hist"], stem + "_envelope.png", torque_limit=res["torque_limit"][0], vel_limit=res["vel_limit"][:3],
-                             soft_torque_limit=res["soft_torque_limit"], soft_vel_limit=res["soft_vel_limit"])
+        subject, keywords = mode.figure_input(res)
+        getattr(module, mode.figure)(subject, stem + mode.figure_suffix, **keywords)
 
 
-def run_feet(a, policy, grid):
-    from go1_gym_learn.eval_metrics import feet
-    for preset in a.presets:
-        res = feet.run_foot_sweep(policy, preset, grid, num_envs=a.envs, steps=a.steps, warmup_steps=a.warmup_steps, seed=a.seed, terrain=a.terrain)
-        stem = os.path.join(a.out, "eval", preset)
-        with open(stem + "_feet.json", "w") as f:
-            json.dump(feet.foot_to_json(res), f, indent=1)
-        text = f"### {preset}: {a.envs} environments, {a.steps} steps, vx {a.vx}, foot loading\n\n" + feet.foot_markdown_table(res) + "\n"
-        print(text)
-        with open(stem + "_feet.md", "a") as f:
-            f.write(text + "\n")
-        feet.plot_grf(res, stem + "_grf.png")
-
-
-def run_trunk(a, policy, grid):
-    from go1_gym_learn.eval_metrics import trunk
-    for preset in a.presets:
-        res = trunk.run_trunk_sweep(policy, preset, grid, num_envs=a.envs, steps=a.steps, warmup_steps=a.warmup_steps, seed=a.seed, terrain=a.terrain,
-                                    segment_steps=a.segment_steps, tilt_limit=a.tilt_limit)
-        stem = os.path.join(a.out, "eval", preset)
-        with open(stem + "_trunk.json", "w") as f:
-            json.dump(trunk.trunk_to_json(res), f, indent=1)
-        text = f"### {preset}: {a.envs} environments, {a.steps} steps, vx {a.vx}, trunk motion\n\n" + trunk.trunk_markdown_table(res) + "\n"
-        print(text)
-        with open(stem + "_trunk.md", "a") as f:
-            f.write(text + "\n")
-        trunk.plot_tilt(res, stem + "_tilt.png")
-
-
-def run_gait(a, policy, grid):
-    from go1_gym_learn.eval_metrics import gait
-    for preset in a.presets:
-        res = gait.run_gait_sweep(policy, preset, grid, num_envs=a.envs, steps=a.steps, warmup_steps=a.warmup_steps, seed=a.seed, terrain=a.terrain,
-                                  min_stride_steps=a.min_stride_steps, max_stride_steps=a.max_stride_steps)
-        stem = os.path.join(a.out, "eval", preset)
-        with open(stem + "_gait.json", "w") as f:
-            json.dump(gait.gait_to_json(res), f, indent=1)
-        text = f"### {preset}: {a.envs} environments, {a.steps} steps, vx {a.vx}, gaits {a.gaits}, inter-leg coordination\n\n" + gait.gait_markdown_table(res) + "\n"
-        print(text)
-        with open(stem + "_gait.md", "a") as f:
-            f.write(text + "\n")
-        gait.plot_gait(res, stem + "_gait.png")
-
-
-def run_spectrum(a, policy, grid):
-    from go1_gym_learn.eval_metrics import spectrum
-    for preset in a.presets:
-        res = spectrum.run_spectrum_sweep(policy, preset, grid, num_envs=a.envs, steps=a.steps, warmup_steps=a.warmup_steps, seed=a.seed, terrain=a.terrain,
-                                          segment_steps=a.segment_steps, high_freq=a.high_freq, taper=a.taper)
-        stem = os.path.join(a.out, "eval", preset)
-        with open(stem + "_spectrum.json", "w") as f:
-            json.dump(spectrum.spectrum_to_json(res), f, indent=1)
-        text = (f"### {preset}: {a.envs} environments, {a.steps} steps, vx {a.vx}, spectra over {a.segment_steps}-step segments ({a.taper})\n\n" +
-                spectrum.spectrum_markdown_table(res) + "\n")
-        print(text)
-        with open(stem + "_spectrum.md", "a") as f:
-            f.write(text + "\n")
-        spectrum.plot_spectrum(res, stem + "_spectrum.png")
-
-
-def run_rewards(a, policy, grid):
-    from go1_gym_learn.eval_metrics import rewards
-    for preset in a.presets:
-        res = rewards.run_reward_sweep(policy, preset, grid, num_envs=a.envs, steps=a.steps, warmup_steps=a.warmup_steps, seed=a.seed, terrain=a.terrain)
-        stem = os.path.join(a.out, "eval", preset)
-        with open(stem + "_rewards.json", "w") as f:
-            json.dump(rewards.reward_to_json(res), f, indent=1)
-        text = f"### {preset}: {a.envs} environments, {a.steps} steps, vx {a.vx}, reward by term (mean per step, share)\n\n" + rewards.reward_table(res) + "\n"
-        print(text)
-        with open(stem + "_rewards.md", "a") as f:
-            f.write(text + "\n")
-        rewards.plot_reward_shares(res, stem + "_rewards.png")
-
-
-def run_placement(a, policy, axes):
-    from go1_gym_learn.eval_metrics import placement
-    for preset in a.presets:
-        res = placement.run_placement_sweep(policy, preset, axes, num_envs=a.envs, steps=a.steps, warmup_steps=a.warmup_steps, seed=a.seed, terrain=a.terrain,
-                                            map_cell=a.map_cell)
-        stem = os.path.join(a.out, "eval", preset)
-        with open(stem + "_placement.json", "w") as f:
-            json.dump(placement.placement_to_json(res), f, indent=1)
-        text = f"### {preset}: {a.envs} environments, {a.steps} steps, axes {axes}, foot placement\n\n" + placement.placement_table(res) + "\n"
-        print(text)
-        with open(stem + "_placement.md", "a") as f:
-            f.write(text + "\n")
-        placement.plot_footprints(res, stem + "_footprints.png")
+run_joints = functools.partial(run_mode, MODE["joints"])                     # run_X(a, policy, grid): each mode under a name of its own
+run_feet = functools.partial(run_mode, MODE["feet"])
+run_trunk = functools.partial(run_mode, MODE["trunk"])
+run_rewards = functools.partial(run_mode, MODE["rewards"])
+run_gait = functools.partial(run_mode, MODE["coordination"])
+run_spectrum = functools.partial(run_mode, MODE["spectrum"])
+run_placement = functools.partial(run_mode, MODE["placement"])              # (its grid is the --axis product)
 
 
 def behaviour_axes(a):
@@ -473,20 +421,9 @@ def main(argv=None):
         return run_push(a, policy)
     if a.tiles:
         return run_terrain(a, policy)
-    if a.joints:
-        return run_joints(a, policy, grid)
-    if a.feet:
-        return run_feet(a, policy, grid)
-    if a.trunk:
-        return run_trunk(a, policy, grid)
-    if a.coordination:
-        return run_gait(a, policy, grid)
-    if a.spectrum:
-        return run_spectrum(a, policy, grid)
-    if a.rewards:
-        return run_rewards(a, policy, grid)
-    if a.placement:
-        return run_placement(a, policy, behaviour_axes(a))
+    for mode in MODES:
+        if getattr(a, mode.dest):
+            return run_mode(mode, a, policy, behaviour_axes(a) if mode.axes else grid)
     if a.behaviour:
         from go1_gym_learn.eval_metrics import behaviour
         axes = behaviour_axes(a)

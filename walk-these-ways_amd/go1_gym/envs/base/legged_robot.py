@@ -136,6 +136,27 @@ class _SimFaults(_LazyMapping):
 
 
 class LeggedRobot(BaseTask):
+    # The measurement families, one row each, in the order step() launches them: the name load_state() reports, the attribute the
+    # family object is kept under, the host module and the class it is made of (the module is imported by the family's first start_*()),
+    # and the method step() calls while the family is armed.  Two rows have none: the behaviour table is folded inside the scalar
+    # table's branch only, and the reward family's accumulate() takes the gravity of the step just taken; step() spells both out.
+    _FAMILIES = (("metrics", "_metrics", "go1eval_host", "Go1Eval", "accumulate"),
+                 ("behaviour", "_behaviour", "go1eval_host", "Go1Behaviour", None),
+                 ("trace", "_trace", "go1eval_host", "Go1Trace", "record"),
+                 ("terrain", "_traversal", "go1eval_host", "Go1Terrain", "accumulate"),
+                 ("joints", "_joints", "go1eval_host", "Go1Joints", "accumulate"),
+                 ("feet", "_feet", "go1feet_host", "Go1Feet", "accumulate"),
+                 ("trunk", "_trunk", "go1trunk_host", "Go1Trunk", "accumulate"),
+                 ("gait", "_gait", "go1gait_host", "Go1Gait", "accumulate"),
+                 ("spectrum", "_spectrum", "go1spectrum_host", "Go1Spectrum", "accumulate"),
+                 ("placement", "_place", "go1place_host", "Go1Place", "accumulate"),
+                 ("rewards", "_reward", "go1reward_host", "Go1Reward", None))
+    _STEPPED = tuple((attr, method) for _, attr, _, _, method in _FAMILIES if method)
+    # load_state() is refused while one of them is armed: their accumulators are not part of a saved state
+    _STATE_FAMILIES = tuple((name, attr) for name, attr, _, _, _ in _FAMILIES)
+    _HOST = {attr: (module, cls) for _, attr, module, cls, _ in _FAMILIES}
+    _HOST["_push"] = ("go1eval_host", "Go1Push")          # made by the first push_robots(); neither stepped nor a state family
+
     def __init__(self, cfg, sim_params, physics_engine, sim_device, headless, eval_cfg=None,
                  initial_dynamics_dict=None):
         self.cfg = cfg
@@ -147,18 +168,8 @@ class LeggedRobot(BaseTask):
         self.initial_dynamics_dict = initial_dynamics_dict
         self._render = None               # go1render_host.Go1Render, created by the first start_recording() / render()
         self._frames = [[], []]           # per camera: the last complete recording handed out
-        self._metrics = None              # go1eval_host.Go1Eval, created by the first start_metrics()
-        self._behaviour = None            # go1eval_host.Go1Behaviour, created by the first start_metrics(behaviour=True)
-        self._trace = None                # go1eval_host.Go1Trace, created by the first start_trace()
-        self._push = None                 # go1eval_host.Go1Push, created by the first push_robots()
-        self._traversal = None            # go1eval_host.Go1Terrain, created by the first start_terrain_metrics()
-        self._joints = None               # go1eval_host.Go1Joints, created by the first start_joint_metrics()
-        self._feet = None                 # go1feet_host.Go1Feet, created by the first start_foot_metrics()
-        self._trunk = None                # go1trunk_host.Go1Trunk, created by the first start_trunk_metrics()
-        self._gait = None                 # go1gait_host.Go1Gait, created by the first start_gait_metrics()
-        self._spectrum = None             # go1spectrum_host.Go1Spectrum, created by the first start_spectrum_metrics()
-        self._place = None                # go1place_host.Go1Place, created by the first start_placement_metrics()
-        self._reward = None               # go1reward_host.Go1Reward, created by the first start_reward_metrics()
+        for attr in self._HOST:           # _metrics ... _reward and _push: each made by the first start_*() / push_robots() of its family
+            setattr(self, attr, None)
         self._state = None                # go1state_host.Go1State, created by the first save_state() / load_state()
         if eval_cfg is not None:          # reference legged_robot.py:41-42
             self._parse_cfg(eval_cfg)
@@ -450,26 +461,12 @@ class LeggedRobot(BaseTask):
             actions = actions.contiguous()
         self.sim.step(actions)
         self._record_step()
-        if self._metrics is not None and self._metrics.armed:
-            self._metrics.accumulate()
-            if self._behaviour is not None and self._behaviour.armed:
-                self._behaviour.accumulate()
-        if self._trace is not None and self._trace.armed:
-            self._trace.record()
-        if self._traversal is not None and self._traversal.armed:
-            self._traversal.accumulate()
-        if self._joints is not None and self._joints.armed:
-            self._joints.accumulate()
-        if self._feet is not None and self._feet.armed:
-            self._feet.accumulate()
-        if self._trunk is not None and self._trunk.armed:
-            self._trunk.accumulate()
-        if self._gait is not None and self._gait.armed:
-            self._gait.accumulate()
-        if self._spectrum is not None and self._spectrum.armed:
-            self._spectrum.accumulate()
-        if self._place is not None and self._place.armed:
-            self._place.accumulate()
+        for attr, method in self._STEPPED:
+            family = getattr(self, attr)
+            if family is not None and family.armed:
+                getattr(family, method)()
+                if attr == "_metrics" and self._behaviour is not None and self._behaviour.armed:      # (only beside the scalar table)
+                    self._behaviour.accumulate()
         if self._reward is not None and self._reward.armed:
             self._reward.accumulate(H.gravity_at(self.sim_config, self.common_step_counter))     # (the gravity of the step just taken)
         if self._curriculum_sync and (self.common_step_counter + 1) % self.sim_config.curriculum_update_interval == 0:
@@ -615,13 +612,14 @@ class LeggedRobot(BaseTask):
         if self.buffers.device.type != "cuda":
             raise NotImplementedError(f"{what}(): the metrics are a HIP library; this simulator's buffers are not on a GPU")
 
-    def _family(self, what, attr, make):
-        """for the hook `what`: the family object kept under `attr`, made by make(go1eval_host) on first use (the library is not
-        imported before that)"""
+    def _family(self, what, attr, *args, **kwargs):
+        """for the hook `what`: the family object kept under `attr`, made on first use as its class of _FAMILIES on the simulator's
+        configuration and buffers and the arguments given (its host module is not imported before that)"""
         self._need_gpu_metrics(what)
         if getattr(self, attr) is None:
-            import go1eval_host
-            setattr(self, attr, make(go1eval_host))
+            import importlib
+            module, cls = self._HOST[attr]
+            setattr(self, attr, getattr(importlib.import_module(module), cls)(self.sim_config, self.buffers, *args, **kwargs))
         return getattr(self, attr)
 
     def _started(self, what, attr, start):
@@ -642,9 +640,9 @@ class LeggedRobot(BaseTask):
         """begin a measurement: `groups` = one int per environment (the row of the result table it counts towards, -1 = not
         evaluated); steps with episode_length_buf <= warmup_steps count towards no metric.  behaviour=True also arms the
         behaviour table (gait, body height, attitude, foot placement and stride tracking): one more launch per step"""
-        self._family("start_metrics", "_metrics", lambda G: G.Go1Eval(self.sim_config, self.buffers)).arm(groups, warmup_steps)
+        self._family("start_metrics", "_metrics").arm(groups, warmup_steps)
         if behaviour:
-            self._family("start_metrics", "_behaviour", lambda G: G.Go1Behaviour(self.sim_config, self.buffers, self.dt)).arm(groups, warmup_steps)
+            self._family("start_metrics", "_behaviour", self.dt).arm(groups, warmup_steps)
         elif self._behaviour is not None:
             self._behaviour.disarm()
             self._behaviour.table = None          # a measurement without the behaviour table reads none
@@ -668,8 +666,7 @@ class LeggedRobot(BaseTask):
     def start_trace(self, env_ids=None, capacity=None):
         """begin a trace of the environments `env_ids` (None: all) with room for `capacity` steps (default: an episode,
         max_episode_length + 2); steps beyond the capacity are not recorded"""
-        trace = self._family("start_trace", "_trace", lambda G: G.Go1Trace(self.sim_config, self.buffers))
-        trace.arm(env_ids, int(self.max_episode_length) + 2 if capacity is None else capacity)
+        self._family("start_trace", "_trace").arm(env_ids, int(self.max_episode_length) + 2 if capacity is None else capacity)
 
     def stop_trace(self):
         """stop recording; what was recorded stays readable"""
@@ -691,7 +688,7 @@ class LeggedRobot(BaseTask):
         """add a velocity step to the base of the environments `env_ids` (None: all, in order) now, between two step() calls:
         push (K, 4) array or tensor of forward, left (the robot's heading frame), up (m/s) and yaw rate (rad/s) steps.  One launch
         on the simulator's stream; the table is checked on the host first (finite, no id twice, ids in range)."""
-        pusher = self._family("push_robots", "_push", lambda G: G.Go1Push(self.sim_config, self.buffers))
+        pusher = self._family("push_robots", "_push")
         pusher.load(push, env_ids)
         pusher.launch()
 
@@ -738,8 +735,7 @@ class LeggedRobot(BaseTask):
         warmup_steps fold no metric"""
         ter = self.cfg.terrain
         tile = (ter.terrain_length, ter.terrain_width) if ter.mesh_type in ("heightfield", "trimesh") else (self.cfg.env.env_spacing,) * 2
-        traversal = self._family("start_terrain_metrics", "_traversal", lambda G: G.Go1Terrain(self.sim_config, self.buffers, self.dt, *tile))
-        traversal.arm(groups, warmup_steps)
+        self._family("start_terrain_metrics", "_traversal", self.dt, *tile).arm(groups, warmup_steps)
 
     def stop_terrain_metrics(self):
         """stop folding steps; what was measured stays readable"""
@@ -759,9 +755,8 @@ class LeggedRobot(BaseTask):
         rewards.soft_torque_limit x the simulator's torque limit and rewards.soft_dof_vel_limit x the URDF's speed limit (a factor
         the configuration does not carry is 1)"""
         rewards = self.cfg.rewards
-        joints = self._family("start_joint_metrics", "_joints", lambda G: G.Go1Joints(
-            self.sim_config, self.buffers, self.dt, H._DOF_VELOCITY, soft_torque_limit=float(getattr(rewards, "soft_torque_limit", 1.0)),
-            soft_vel_limit=float(getattr(rewards, "soft_dof_vel_limit", 1.0))))
+        joints = self._family("start_joint_metrics", "_joints", self.dt, H._DOF_VELOCITY, soft_torque_limit=float(getattr(rewards, "soft_torque_limit", 1.0)),
+                              soft_vel_limit=float(getattr(rewards, "soft_dof_vel_limit", 1.0)))
         joints.arm(groups, warmup_steps)
 
     def stop_joint_metrics(self):
@@ -781,11 +776,7 @@ class LeggedRobot(BaseTask):
         """begin a foot-loading measurement: `groups` = one int per environment (the row of the result tables it counts towards, -1 = not
         evaluated); steps with episode_length_buf <= warmup_steps fold nothing and break every stance.  The ground's friction and
         max_contact_force are the simulator's (terrain.static_friction, rewards.max_contact_force)"""
-        self._need_gpu_metrics("start_foot_metrics")
-        if self._feet is None:
-            import go1feet_host
-            self._feet = go1feet_host.Go1Feet(self.sim_config, self.buffers, self.dt)
-        self._feet.arm(groups, warmup_steps)
+        self._family("start_foot_metrics", "_feet", self.dt).arm(groups, warmup_steps)
 
     def stop_foot_metrics(self):
         """stop folding steps; what was measured stays readable"""
@@ -807,11 +798,7 @@ class LeggedRobot(BaseTask):
         of a drift segment; 50 is 1 s, two strides or more at 2 Hz and above, so the sway within a stride cancels.  tilt_limit: the sine
         beyond which a step counts as tilt_exceeded; 0.25 (about 14.5 degrees) is a placeholder, as the push family's band is: no
         measurement of a robot's falls stands behind it"""
-        self._need_gpu_metrics("start_trunk_metrics")
-        if self._trunk is None:
-            import go1trunk_host
-            self._trunk = go1trunk_host.Go1Trunk(self.sim_config, self.buffers, self.dt)
-        self._trunk.arm(groups, warmup_steps, segment_steps=segment_steps, tilt_limit=tilt_limit)
+        self._family("start_trunk_metrics", "_trunk", self.dt).arm(groups, warmup_steps, segment_steps=segment_steps, tilt_limit=tilt_limit)
 
     def stop_trunk_metrics(self):
         """stop folding steps; what was measured stays readable"""
@@ -832,11 +819,7 @@ class LeggedRobot(BaseTask):
         evaluated); steps with episode_length_buf <= warmup_steps fold nothing and end an open stride.  min_stride_steps: a touchdown
         of FL sooner after the stride's opening is chatter (1: no debounce); max_stride_steps: a stride that outgrows it is dropped
         (100 is 2 s)"""
-        self._need_gpu_metrics("start_gait_metrics")
-        if self._gait is None:
-            import go1gait_host
-            self._gait = go1gait_host.Go1Gait(self.sim_config, self.buffers)
-        self._gait.arm(groups, warmup_steps, min_stride_steps=min_stride_steps, max_stride_steps=max_stride_steps)
+        self._family("start_gait_metrics", "_gait").arm(groups, warmup_steps, min_stride_steps=min_stride_steps, max_stride_steps=max_stride_steps)
 
     def stop_gait_metrics(self):
         """stop folding steps; what was measured stays readable"""
@@ -857,11 +840,7 @@ class LeggedRobot(BaseTask):
         evaluated); a step with episode_length_buf <= warmup_steps or a reset spoils the segment it falls in.  segment_steps: even, 8 to
         128 policy steps per segment (100 is 2 s: 0.5 Hz bins up to 25 Hz); high_freq: high_share counts the bins from this frequency on
         (10 Hz is a placeholder, nothing measured stands behind it); taper: "hann" or "boxcar" """
-        self._need_gpu_metrics("start_spectrum_metrics")
-        if self._spectrum is None:
-            import go1spectrum_host
-            self._spectrum = go1spectrum_host.Go1Spectrum(self.sim_config, self.buffers, self.dt)
-        self._spectrum.arm(groups, warmup_steps, segment_steps=segment_steps, high_freq=high_freq, taper=taper)
+        self._family("start_spectrum_metrics", "_spectrum", self.dt).arm(groups, warmup_steps, segment_steps=segment_steps, high_freq=high_freq, taper=taper)
 
     def stop_spectrum_metrics(self):
         """stop recording steps; what was measured stays readable.  A segment left open is discarded, not counted as dropped"""
@@ -881,11 +860,7 @@ class LeggedRobot(BaseTask):
         """begin a foot-placement measurement: `groups` = one int per environment (the row of the result tables it counts towards, -1 = not
         evaluated); steps with episode_length_buf <= warmup_steps fold nothing and end every open stance and stride.  map_cell: the side
         of a cell of the footprint map in metres (0.03 is a placeholder, nothing measured stands behind it: the map spans +-0.12 m)"""
-        self._need_gpu_metrics("start_placement_metrics")
-        if self._place is None:
-            import go1place_host
-            self._place = go1place_host.Go1Place(self.sim_config, self.buffers)
-        self._place.arm(groups, warmup_steps, map_cell=map_cell)
+        self._family("start_placement_metrics", "_place").arm(groups, warmup_steps, map_cell=map_cell)
 
     def stop_placement_metrics(self):
         """stop folding steps; what was measured stays readable"""
@@ -905,11 +880,7 @@ class LeggedRobot(BaseTask):
     def start_reward_metrics(self, groups, warmup_steps=0):
         """begin a reward measurement: `groups` = one int per environment (the row of the result tables it counts towards, -1 = not
         evaluated); steps with episode_length_buf <= warmup_steps fold nothing"""
-        self._need_gpu_metrics("start_reward_metrics")
-        if self._reward is None:
-            import go1reward_host
-            self._reward = go1reward_host.Go1Reward(self.sim_config, self.buffers, self.reward_names)
-        self._reward.arm(groups, warmup_steps)
+        self._family("start_reward_metrics", "_reward", self.reward_names).arm(groups, warmup_steps)
 
     def stop_reward_metrics(self):
         """stop folding steps; what was measured stays readable"""
@@ -940,10 +911,6 @@ class LeggedRobot(BaseTask):
     # into chosen environments (one launch), re-phased to where the lag and history rings stand now.  Neither runs during step(): an
     # environment that never saves imports nothing.  What a snapshot does not hold: the terrain, the configuration, the host-backend
     # curriculum objects (device_curriculum=False), and the accumulators of the measurement families.
-    _STATE_FAMILIES = (("metrics", "_metrics"), ("behaviour", "_behaviour"), ("trace", "_trace"), ("terrain", "_traversal"),
-                       ("joints", "_joints"), ("feet", "_feet"), ("trunk", "_trunk"), ("gait", "_gait"), ("spectrum", "_spectrum"),
-                       ("placement", "_place"), ("rewards", "_reward"))
-
     def _stater(self, what):
         if self._state is None:
             if self.buffers.device.type != "cuda":

@@ -222,9 +222,8 @@ def behaviour_markdown_table(result, metrics=tuple(BEHAVIOUR_NAMES)):
 
 def behaviour_to_json(result):
     """the JSON form of a run_behaviour_sweep result"""
-    fields = ["count", "mean", "std", "min", "max", "nonfinite"]
     return dict(preset=result["preset"], num_envs=result["num_envs"], steps=result["steps"], warmup_steps=result["warmup_steps"],
-                seed=result["seed"], cells=result["cells"], fields=fields,
+                seed=result["seed"], cells=result["cells"], fields=list(sweep.FIELDS),
                 metrics={k: v.tolist() for k, v in result["metrics"].items()},
                 behaviour={k: v.tolist() for k, v in result["behaviour"].items()},
                 group_fields=["envs", "steps", "episodes_terminated", "episodes_timed_out", "fall_rate"], groups=result["groups"].tolist())

@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import sweep
+from .sweep import number
 
 FOOT_TERMS = ["contact", "force_normal", "force_tangent", "friction_use", "force_excess", "impact_vel_sq", "touchdown_speed", "touchdown_force"]
 FEET_METRICS = FOOT_TERMS + ["stance_peak_force", "stance_impulse", "stance_slip", "stance_time"]
@@ -56,21 +57,7 @@ def run_foot_sweep(policy, preset, grid=None, num_envs=4096, steps=500, warmup_s
     "metrics": the scalar table {name: (cells, 6)}, "groups": (cells, 5), "body_weight": N, the model's total mass plus the mean
     payload times g, "terrain_friction", "max_contact_force", ...}."""
     cells = sweep.grid_cells(grid or sweep.DEFAULT_GRID)
-    env, _ = sweep.build_eval_env(preset, num_envs, seed, terrain)
-    if hasattr(policy, "eval"):
-        policy.eval()
-    base = env.env
-    obs, group, commands = sweep.prepare(env, cells)
-    base.start_metrics(group, warmup_steps=warmup_steps)
-    base.start_foot_metrics(group, warmup_steps=warmup_steps)
-    sweep.rollout(env, policy, obs, steps, commands)
-    base.stop_metrics()
-    base.stop_foot_metrics()
-    if not sweep.commands_held(env, commands):
-        raise RuntimeError("run_foot_sweep: an environment left its grid cell's commands during the rollout")
-    scalar = base.read_metrics()
-    groups = scalar.pop("groups")
-    res = base.read_foot_metrics()
+    base, _, scalar, groups, res = sweep.run_beside_scalar("run_foot_sweep", "foot", policy, preset, cells, num_envs, steps, warmup_steps, seed, terrain)
     c = base._feet.cfg
     mass = total_mass() + float(base.payloads.mean())
     return dict(preset=preset, cells=cells, feet=res["metrics"], feet_groups=res["groups"], profile=res["profile"],
@@ -89,10 +76,6 @@ def load_shares(profile, profile_count):
         return mean / mean.sum(axis=1, keepdims=True)
 
 
-def _number(x, fmt):
-    return format(x, fmt) if np.isfinite(x) else "–"
-
-
 def foot_markdown_table(result):
     """one row per cell and foot: duty factor, mean and peak vertical force (over every loaded step) in N and in body weights, mean and
     max friction use, mean and max touchdown speed [m/s], impulse [N s] and slip [m] per stance, the foot's share of the total vertical
@@ -107,11 +90,11 @@ def foot_markdown_table(result):
         for f, foot in enumerate(result["foot_names"]):
             at = lambda name, field: feet[name][g][f][field]
             peak = at("force_normal", 4)
-            row = [f"{cell[0]:g}", f"{cell[1]:g}", foot, _number(at("contact", 1), ".3f"), _number(at("force_normal", 1), ".1f"),
-                   _number(at("force_normal", 1) / weight, ".3f"), _number(peak, ".1f"), _number(peak / weight, ".3f"),
-                   _number(at("friction_use", 1), ".3f"), _number(at("friction_use", 4), ".3f"), _number(at("touchdown_speed", 1), ".3f"),
-                   _number(at("touchdown_speed", 4), ".3f"), _number(at("stance_impulse", 1), ".2f"), _number(at("stance_slip", 1), ".4f"),
-                   _number(shares[g, f], ".3f"), _number(front, ".3f") if f == 0 else "", _number(left, ".3f") if f == 0 else ""]
+            row = [f"{cell[0]:g}", f"{cell[1]:g}", foot, number(at("contact", 1), ".3f"), number(at("force_normal", 1), ".1f"),
+                   number(at("force_normal", 1) / weight, ".3f"), number(peak, ".1f"), number(peak / weight, ".3f"),
+                   number(at("friction_use", 1), ".3f"), number(at("friction_use", 4), ".3f"), number(at("touchdown_speed", 1), ".3f"),
+                   number(at("touchdown_speed", 4), ".3f"), number(at("stance_impulse", 1), ".2f"), number(at("stance_slip", 1), ".4f"),
+                   number(shares[g, f], ".3f"), number(front, ".3f") if f == 0 else "", number(left, ".3f") if f == 0 else ""]
             lines.append("| " + " | ".join(row) + " |")
     return "\n".join(lines)
 
@@ -121,8 +104,7 @@ def foot_to_json(result):
     clean = lambda a: [clean(x) for x in a] if isinstance(a, list) else (a if a == a else None)
     keep = ("preset", "num_envs", "steps", "warmup_steps", "seed", "dt", "foot_names", "body_weight", "terrain_friction", "max_contact_force")
     out = {k: result[k] for k in keep}
-    out.update(cells=[dict(vx=c[0], yaw=c[1], gait=list(c[2])) for c in result["cells"]], fields=["count", "mean", "std", "min", "max", "nonfinite"],
-               group_fields=["envs", "steps", "resets"], feet={m: clean(np.asarray(t).tolist()) for m, t in result["feet"].items()},
+    out.update(cells=sweep.cells_to_json(result["cells"]), fields=list(sweep.FIELDS), group_fields=["envs", "steps", "resets"], feet={m: clean(np.asarray(t).tolist()) for m, t in result["feet"].items()},
                feet_groups=np.asarray(result["feet_groups"]).tolist(), profile=clean(np.asarray(result["profile"]).tolist()),
                profile_count=np.asarray(result["profile_count"]).tolist(), phase_edges=np.asarray(result["phase_edges"]).tolist(),
                load_share=clean(load_shares(result["profile"], result["profile_count"]).tolist()))

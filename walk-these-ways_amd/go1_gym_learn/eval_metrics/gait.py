@@ -10,6 +10,7 @@ so their resolution is 1/16 cycle), and `classify` names the nearest of `sweep.G
 import numpy as np
 
 from . import sweep
+from .sweep import clean, number
 
 LEGS = ["FR", "RL", "RR"]                                                    # the feet placed within FL's stride
 GAIT_METRICS = ["sync_FL_FR", "sync_FL_RL", "sync_FL_RR", "sync_FR_RL", "sync_FR_RR", "sync_RL_RR"] + \
@@ -77,21 +78,8 @@ def run_gait_sweep(policy, preset, grid=None, num_envs=4096, steps=500, warmup_s
     "phase_centres": (16,), "support_patterns", "metrics": the scalar table {name: (cells, 6)}, "groups": (cells, 5), "min_stride_steps",
     "max_stride_steps", ...}."""
     cells = sweep.grid_cells(grid or sweep.DEFAULT_GRID)
-    env, _ = sweep.build_eval_env(preset, num_envs, seed, terrain)
-    if hasattr(policy, "eval"):
-        policy.eval()
-    base = env.env
-    obs, group, commands = sweep.prepare(env, cells)
-    base.start_metrics(group, warmup_steps=warmup_steps)
-    base.start_gait_metrics(group, warmup_steps=warmup_steps, min_stride_steps=min_stride_steps, max_stride_steps=max_stride_steps)
-    sweep.rollout(env, policy, obs, steps, commands)
-    base.stop_metrics()
-    base.stop_gait_metrics()
-    if not sweep.commands_held(env, commands):
-        raise RuntimeError("run_gait_sweep: an environment left its grid cell's commands during the rollout")
-    scalar = base.read_metrics()
-    groups = scalar.pop("groups")
-    res = base.read_gait_metrics()
+    base, _, scalar, groups, res = sweep.run_beside_scalar("run_gait_sweep", "gait", policy, preset, cells, num_envs, steps, warmup_steps, seed, terrain,
+                                                           dict(min_stride_steps=min_stride_steps, max_stride_steps=max_stride_steps))
     return dict(preset=preset, cells=cells, gait=res["metrics"], gait_groups=res["groups"], support_hist=res["support_hist"], phase_hist=res["phase_hist"],
                 phase_centres=res["phase_centres"], support_patterns=res["support_patterns"], metrics=scalar, groups=groups,
                 min_stride_steps=int(min_stride_steps), max_stride_steps=int(max_stride_steps), num_envs=num_envs, steps=steps, warmup_steps=warmup_steps,
@@ -129,10 +117,6 @@ def cell_summary(result, g):
                 strides_dropped=float(result["gait_groups"][g][4]))
 
 
-def _number(x, fmt):
-    return format(x, fmt) if np.isfinite(x) else "–"
-
-
 def gait_markdown_table(result):
     """one row per cell: the commanded gait and the realised class (with its distance), per leg the touchdown phase within FL's stride
     commanded / realised / error (the device's mean +- std, or ~ the histogram's where the errors wrap), the resultant lengths, the
@@ -143,32 +127,24 @@ def gait_markdown_table(result):
     lines = ["| " + " | ".join(head) + " |", "|" + "---|" * len(head)]
     for g, cell in enumerate(result["cells"]):
         s = cell_summary(result, g)
-        row = [f"{cell[0]:g}", f"{cell[1]:g}", s["commanded_gait"], s["class"], _number(s["class_distance"], ".3f")]
+        row = [f"{cell[0]:g}", f"{cell[1]:g}", s["commanded_gait"], s["class"], number(s["class_distance"], ".3f")]
         for k in range(3):
-            shown = ("~" + _number(s["err"][k], "+.3f")) if s["err_from_histogram"][k] else (_number(s["err"][k], "+.3f") + " ± " + _number(s["err_std"][k], ".3f"))
-            row.append(f"{s['commanded'][k]:.3f} / {_number(s['realised'][k], '.3f')} / {shown}")
-        row.append(" / ".join(_number(x, ".2f") for x in s["resultant"]))
-        row += [_number(s["sync"][k], ".3f") for k in ("diagonal", "lateral", "fore_hind")]
-        row += [_number(s["support"][k], ".3f") for k in SUPPORT_SHARES]
-        row += [" / ".join(_number(x, ".2f") for x in s["touchdowns"]), f"{s['strides']:.0f}", f"{s['strides_dropped']:.0f}"]
+            shown = ("~" + number(s["err"][k], "+.3f")) if s["err_from_histogram"][k] else (number(s["err"][k], "+.3f") + " ± " + number(s["err_std"][k], ".3f"))
+            row.append(f"{s['commanded'][k]:.3f} / {number(s['realised'][k], '.3f')} / {shown}")
+        row.append(" / ".join(number(x, ".2f") for x in s["resultant"]))
+        row += [number(s["sync"][k], ".3f") for k in ("diagonal", "lateral", "fore_hind")]
+        row += [number(s["support"][k], ".3f") for k in SUPPORT_SHARES]
+        row += [" / ".join(number(x, ".2f") for x in s["touchdowns"]), f"{s['strides']:.0f}", f"{s['strides_dropped']:.0f}"]
         lines.append("| " + " | ".join(row) + " |")
     return "\n".join(lines)
 
 
 def gait_to_json(result):
     """the JSON form of a run_gait_sweep result (NaN and infinities as null)"""
-    def clean(a):
-        if isinstance(a, dict):
-            return {k: clean(v) for k, v in a.items()}
-        if isinstance(a, (list, tuple)):
-            return [clean(x) for x in a]
-        if isinstance(a, (bool, str)):
-            return a
-        return a if np.isfinite(a) else None
     keep = ("preset", "num_envs", "steps", "warmup_steps", "seed", "dt", "min_stride_steps", "max_stride_steps")
     out = {k: result[k] for k in keep}
-    out.update(cells=[dict(vx=c[0], yaw=c[1], gait=list(c[2]), gait_name=gait_name(c[2])) for c in result["cells"]],
-               fields=["count", "mean", "std", "min", "max", "nonfinite"], group_fields=["envs", "steps", "resets", "strides", "strides_dropped"],
+    out.update(cells=sweep.cells_to_json(result["cells"], gait_name=[gait_name(c[2]) for c in result["cells"]]),
+               fields=list(sweep.FIELDS), group_fields=["envs", "steps", "resets", "strides", "strides_dropped"],
                gait={m: clean(np.asarray(t).tolist()) for m, t in result["gait"].items()}, gait_groups=np.asarray(result["gait_groups"]).tolist(),
                support_hist=np.asarray(result["support_hist"]).tolist(), phase_hist=np.asarray(result["phase_hist"]).tolist(),
                phase_centres=np.asarray(result["phase_centres"]).tolist(), support_patterns=list(result["support_patterns"]), legs=list(LEGS),

@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import sweep
+from .sweep import number
 
 JOINT_TERMS = ["torque_abs", "torque_sq", "vel_abs", "vel_sq", "acc_sq", "power_pos", "power_neg", "pos_limit_excess", "torque_saturated",
                "vel_saturated"]
@@ -42,21 +43,7 @@ def run_joint_sweep(policy, preset, grid=None, num_envs=4096, steps=500, warmup_
     "metrics": the scalar table {name: (cells, 6)}, "groups": (cells, 5), "torque_limit", "vel_limit", "soft_torque_limit",
     "soft_vel_limit", ...}."""
     cells = sweep.grid_cells(grid or sweep.DEFAULT_GRID)
-    env, _ = sweep.build_eval_env(preset, num_envs, seed, terrain)
-    if hasattr(policy, "eval"):
-        policy.eval()
-    base = env.env
-    obs, group, commands = sweep.prepare(env, cells)
-    base.start_metrics(group, warmup_steps=warmup_steps)
-    base.start_joint_metrics(group, warmup_steps=warmup_steps)
-    sweep.rollout(env, policy, obs, steps, commands)
-    base.stop_metrics()
-    base.stop_joint_metrics()
-    if not sweep.commands_held(env, commands):
-        raise RuntimeError("run_joint_sweep: an environment left its grid cell's commands during the rollout")
-    scalar = base.read_metrics()
-    groups = scalar.pop("groups")
-    res = base.read_joint_metrics()
+    base, _, scalar, groups, res = sweep.run_beside_scalar("run_joint_sweep", "joint", policy, preset, cells, num_envs, steps, warmup_steps, seed, terrain)
     c = base._joints.cfg
     return dict(preset=preset, cells=cells, joints=res["metrics"], joint_groups=res["groups"], hist=res["hist"], tau_edges=res["tau_edges"],
                 vel_edges=res["vel_edges"], metrics=scalar, groups=groups, torque_limit=list(c.torque_limit), vel_limit=list(c.vel_limit),
@@ -82,10 +69,6 @@ def pool_cells(table):
                      t[:, :, 5].sum(axis=0)], axis=1)
 
 
-def _number(x, fmt):
-    return format(x, fmt) if np.isfinite(x) else "–"
-
-
 def joint_markdown_table(result):
     """one row per joint over every cell of the sweep: mean and max of |tau| [N m], share of steps at the torque limit, max of |qd|
     [rad/s], share at the speed limit, mean driving and braking power [W], rms acceleration [rad/s^2], and mean and max of the excess
@@ -96,10 +79,10 @@ def joint_markdown_table(result):
             "mean limit excess", "max limit excess"]
     lines = ["| " + " | ".join(head) + " |", "|" + "---|" * len(head)]
     for j, name in enumerate(result["dof_names"]):
-        row = [name, _number(pooled["torque_abs"][j, 1], ".2f"), _number(pooled["torque_abs"][j, 4], ".2f"), _number(pooled["torque_saturated"][j, 1], ".4f"),
-               _number(pooled["vel_abs"][j, 4], ".2f"), _number(pooled["vel_saturated"][j, 1], ".4f"), _number(pooled["power_pos"][j, 1], ".2f"),
-               _number(pooled["power_neg"][j, 1], ".2f"), _number(np.sqrt(pooled["acc_sq"][j, 1]), ".1f"), _number(pooled["pos_limit_excess"][j, 1], ".4f"),
-               _number(pooled["pos_limit_excess"][j, 4], ".4f")]
+        row = [name, number(pooled["torque_abs"][j, 1], ".2f"), number(pooled["torque_abs"][j, 4], ".2f"), number(pooled["torque_saturated"][j, 1], ".4f"),
+               number(pooled["vel_abs"][j, 4], ".2f"), number(pooled["vel_saturated"][j, 1], ".4f"), number(pooled["power_pos"][j, 1], ".2f"),
+               number(pooled["power_neg"][j, 1], ".2f"), number(np.sqrt(pooled["acc_sq"][j, 1]), ".1f"), number(pooled["pos_limit_excess"][j, 1], ".4f"),
+               number(pooled["pos_limit_excess"][j, 4], ".4f")]
         lines.append("| " + " | ".join(row) + " |")
     return "\n".join(lines)
 
@@ -108,8 +91,7 @@ def joint_to_json(result):
     """the JSON form of a run_joint_sweep result"""
     keep = ("preset", "num_envs", "steps", "warmup_steps", "seed", "dt", "dof_names", "torque_limit", "vel_limit", "soft_torque_limit", "soft_vel_limit")
     out = {k: result[k] for k in keep}
-    out.update(cells=[dict(vx=c[0], yaw=c[1], gait=list(c[2])) for c in result["cells"]], fields=["count", "mean", "std", "min", "max", "nonfinite"],
-               group_fields=["envs", "steps", "resets"], joints={m: np.asarray(t).tolist() for m, t in result["joints"].items()},
+    out.update(cells=sweep.cells_to_json(result["cells"]), fields=list(sweep.FIELDS), group_fields=["envs", "steps", "resets"], joints={m: np.asarray(t).tolist() for m, t in result["joints"].items()},
                joint_groups=np.asarray(result["joint_groups"]).tolist(), hist=np.asarray(result["hist"]).tolist(),
                tau_edges=np.asarray(result["tau_edges"]).tolist(), vel_edges=np.asarray(result["vel_edges"]).tolist())
     return out

@@ -14,6 +14,7 @@ import torch
 from go1_gym.utils.math_utils import quat_apply_yaw, quat_conjugate
 
 from . import behaviour, sweep
+from .sweep import clean, number
 
 FEET = ["FL", "FR", "RL", "RR"]
 PLACEMENT_METRICS = ["stance_err_x", "stance_err_y", "swing_err_x", "swing_err_y", "touchdown_x", "touchdown_y", "touchdown_err_x", "touchdown_err_y",
@@ -62,21 +63,8 @@ def run_placement_sweep(policy, preset, axes, num_envs=4096, steps=500, warmup_s
     "map": (cells, 4, 8, 8), "map_edges": (9,), "foot_counts": {"touchdowns", "strides", "map_outside": (cells, 4)}, "metrics": the scalar
     table {name: (cells, 6)}, "groups": (cells, 5), "map_cell", ...}."""
     cells = behaviour.behaviour_cells(axes)
-    env, _ = sweep.build_eval_env(preset, num_envs, seed, terrain)
-    if hasattr(policy, "eval"):
-        policy.eval()
-    base = env.env
-    obs, group, commands = behaviour.prepare(env, cells)
-    base.start_metrics(group, warmup_steps=warmup_steps)
-    base.start_placement_metrics(group, warmup_steps=warmup_steps, map_cell=map_cell)
-    sweep.rollout(env, policy, obs, steps, commands)
-    base.stop_metrics()
-    base.stop_placement_metrics()
-    if not sweep.commands_held(env, commands):
-        raise RuntimeError("run_placement_sweep: an environment left its cell's commands during the rollout")
-    scalar = base.read_metrics()
-    groups = scalar.pop("groups")
-    res = base.read_placement_metrics()
+    base, group, scalar, groups, res = sweep.run_beside_scalar("run_placement_sweep", "placement", policy, preset, cells, num_envs, steps, warmup_steps, seed, terrain,
+                                                               dict(map_cell=map_cell), prepare_cells=behaviour.prepare, cell="cell")
     member = group.cpu().numpy()
     per_foot = lambda name: np.stack([res[name].view(np.uint32)[:, member == g].sum(axis=1).astype(np.float64) for g in range(len(cells))])
     table = behaviour.behaviour_command_table(cells, base.commands.shape[1], "cpu").numpy()
@@ -95,12 +83,8 @@ def commanded(result, g):
     return dict(width=width, length=length, stride_length=stride)
 
 
-def _number(x, fmt):
-    return format(x, fmt) if np.isfinite(x) else "–"
-
-
 def _mean_std(row, fmt="+.3f"):
-    return _number(row[1], fmt) + " ± " + _number(row[2], ".3f")
+    return number(row[1], fmt) + " ± " + number(row[2], ".3f")
 
 
 def placement_table(result):
@@ -119,29 +103,21 @@ def placement_table(result):
             row = lambda name: np.asarray(t[name][g][f], np.float64)
             touchdowns, strides, outside = (float(result["foot_counts"][k][g][f]) for k in ("touchdowns", "strides", "map_outside"))
             line = [f"{cell[n]:g}" for n in names] + [foot, f"{want['width']:.3f} / {want['length']:.3f}", _mean_std(row("touchdown_x")), _mean_std(row("touchdown_y")),
-                    _number(row("touchdown_err_x")[1], "+.3f") + " / " + _number(row("touchdown_err_y")[1], "+.3f"),
-                    _number(row("stance_err_x")[1], "+.3f") + " / " + _number(row("stance_err_y")[1], "+.3f"),
-                    _number(row("swing_err_x")[1], "+.3f") + " / " + _number(row("swing_err_y")[1], "+.3f"), _mean_std(row("stance_sweep")),
-                    _number(row("stride_length")[1], ".3f") + " / " + _number(want["stride_length"], ".3f"),
-                    _number(want["width"] + row("track_width_err")[1], ".3f") + " / " + f"{want['width']:.3f}",
-                    f"{touchdowns:.0f}", f"{strides:.0f}", _number(outside / touchdowns if touchdowns > 0 else float("nan"), ".3f")]
+                    number(row("touchdown_err_x")[1], "+.3f") + " / " + number(row("touchdown_err_y")[1], "+.3f"),
+                    number(row("stance_err_x")[1], "+.3f") + " / " + number(row("stance_err_y")[1], "+.3f"),
+                    number(row("swing_err_x")[1], "+.3f") + " / " + number(row("swing_err_y")[1], "+.3f"), _mean_std(row("stance_sweep")),
+                    number(row("stride_length")[1], ".3f") + " / " + number(want["stride_length"], ".3f"),
+                    number(want["width"] + row("track_width_err")[1], ".3f") + " / " + f"{want['width']:.3f}",
+                    f"{touchdowns:.0f}", f"{strides:.0f}", number(outside / touchdowns if touchdowns > 0 else float("nan"), ".3f")]
             lines.append("| " + " | ".join(line) + " |")
     return "\n".join(lines)
 
 
 def placement_to_json(result):
     """the JSON form of a run_placement_sweep result (NaN and infinities as null)"""
-    def clean(a):
-        if isinstance(a, dict):
-            return {k: clean(v) for k, v in a.items()}
-        if isinstance(a, (list, tuple)):
-            return [clean(x) for x in a]
-        if isinstance(a, (bool, str)):
-            return a
-        return a if np.isfinite(a) else None
     out = {k: result[k] for k in ("preset", "num_envs", "steps", "warmup_steps", "seed", "dt", "map_cell")}
     out.update(cells=result["cells"], commanded=[clean(commanded(result, g)) for g in range(len(result["cells"]))], feet=list(FEET),
-               fields=["count", "mean", "std", "min", "max", "nonfinite"], group_fields=list(PLACEMENT_GROUP_FIELDS),
+               fields=list(sweep.FIELDS), group_fields=list(PLACEMENT_GROUP_FIELDS),
                placement={m: clean(np.asarray(t).tolist()) for m, t in result["placement"].items()},
                placement_groups=np.asarray(result["placement_groups"]).tolist(), map=np.asarray(result["map"]).tolist(),
                map_edges=np.asarray(result["map_edges"]).tolist(), foot_counts={k: np.asarray(v).tolist() for k, v in result["foot_counts"].items()},

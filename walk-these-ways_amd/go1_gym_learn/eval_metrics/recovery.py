@@ -116,10 +116,6 @@ def paired_excess(cells, source, peak, status):
     return out
 
 
-def _mean_std(row):
-    return f"{row[1]:.3g} ± {row[2]:.2g}" if row[0] > 0 else "–"
-
-
 def recovery_markdown_table(result):
     """one row per cell: ok / fell / baseline reset / not held, the fall rate fell / (ok + fell), then over the environments with
     status 0 mean +- std of the peak velocity error and of the recovery time (over those that recovered) and the recovered share"""
@@ -133,7 +129,7 @@ def recovery_markdown_table(result):
     for g, (magnitude, direction) in enumerate(result["cells"]):
         ok, spoiled, moved, fell = (int(x) for x in result["groups"][g, 1:5])
         row = [f"{magnitude:g}", f"{direction:g}", f"{ok} / {fell} / {spoiled} / {moved}", f"{fell / (ok + fell):.3f}" if ok + fell > 0 else "–"]
-        row += [_mean_std(r["peak_vel_err"][g]), _mean_std(r["recovery_time"][g]), f"{r['recovered'][g, 1]:.3f}" if r["recovered"][g, 0] > 0 else "–"]
+        row += [sweep.mean_std(r["peak_vel_err"][g]), sweep.mean_std(r["recovery_time"][g]), f"{r['recovered'][g, 1]:.3f}" if r["recovered"][g, 0] > 0 else "–"]
         if excess is not None:
             row.append(f"{excess[g][0]:.3g} ± {excess[g][1]:.2g} ({int(excess[g][2])})" if excess[g][2] > 0 else "–")
         lines.append("| " + " | ".join(row) + " |")
@@ -144,7 +140,7 @@ def recovery_to_json(result):
     """the JSON form of a run_push_sweep result (without the per-environment values and the trace)"""
     keep = ("preset", "num_envs", "settle_steps", "pre", "window", "smooth", "band", "hold", "dt", "seed")
     out = {k: result[k] for k in keep}
-    out.update(cells=[dict(magnitude=m, direction_deg=d) for m, d in result["cells"]], fields=["count", "mean", "std", "min", "max", "nonfinite"],
+    out.update(cells=[dict(magnitude=m, direction_deg=d) for m, d in result["cells"]], fields=list(sweep.FIELDS),
                group_fields=["envs", "ok", "baseline_reset", "not_held", "fell"],
                recovery={m: t.tolist() for m, t in result["recovery"].items()}, groups=result["groups"].tolist(),
                status_counts=[int((result["status"] == k).sum()) for k in (0, 1, 2, 3)])

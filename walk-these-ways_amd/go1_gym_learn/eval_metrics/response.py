@@ -91,10 +91,6 @@ def select_envs(trace, envs):
     return out
 
 
-def _mean_std(row):
-    return f"{row[1]:.3g} ± {row[2]:.2g}" if row[0] > 0 else "–"
-
-
 def response_markdown_table(result, signal=None):
     """one row per cell for one signal (default: the first): ok / fell / not held, the reached and settled fractions of the
     environments with status 0, then mean +- std of rise time, settling time, overshoot and steady-state error"""
@@ -107,7 +103,7 @@ def response_markdown_table(result, signal=None):
         ok, fell, moved = (int(x) for x in result["groups"][g, 1:4])
         row = [f"{result['from_value']} → {value}", signal, f"{ok} / {fell} / {moved}"]
         row += [f"{r[m][g, 1]:.3f}" if r[m][g, 0] > 0 else "–" for m in ("reached", "settled")]
-        row += [_mean_std(r[m][g]) for m in ("rise_time", "settling_time", "overshoot", "steady_state_err")]
+        row += [sweep.mean_std(r[m][g]) for m in ("rise_time", "settling_time", "overshoot", "steady_state_err")]
         lines.append("| " + " | ".join(row) + " |")
     return "\n".join(lines)
 
@@ -117,7 +113,7 @@ def response_to_json(result):
     keep = ("preset", "command", "from_value", "cells", "signals", "num_envs", "settle_steps", "pre", "window", "smooth", "band", "hold",
             "tail", "dt", "seed")
     out = {k: result[k] for k in keep}
-    out.update(fields=["count", "mean", "std", "min", "max", "nonfinite"], group_fields=["envs", "ok", "reset", "not_held"],
+    out.update(fields=list(sweep.FIELDS), group_fields=["envs", "ok", "reset", "not_held"],
                response={s: {m: t.tolist() for m, t in metrics.items()} for s, metrics in result["response"].items()},
                groups=result["groups"].tolist(), status_counts=[int((result["status"] == k).sum()) for k in (0, 1, 2)])
     return out

@@ -9,6 +9,7 @@ nothing in the step loop reads from the device.
 import numpy as np
 
 from . import sweep
+from .sweep import clean, number
 
 EXTRA_ROWS = ("sum", "positive", "negative", "total")
 GROUP_FIELDS = ["envs", "measured", "reset", "teleported"]
@@ -20,30 +21,12 @@ def run_reward_sweep(policy, preset, grid=None, num_envs=4096, steps=500, warmup
     "terms": {name: (cells, 6)}, "sum" / "positive" / "negative" / "total": (cells, 6), "share": {name: (cells,)}, "reward_groups":
     (cells, 4) array of envs, measured, reset, teleported env-steps, "metrics": the scalar table, "groups": (cells, 5), ...}."""
     cells = sweep.grid_cells(grid or sweep.DEFAULT_GRID)
-    env, _ = sweep.build_eval_env(preset, num_envs, seed, terrain)
-    if hasattr(policy, "eval"):
-        policy.eval()
-    base = env.env
-    obs, group, commands = sweep.prepare(env, cells)
-    base.start_metrics(group, warmup_steps=warmup_steps)
-    base.start_reward_metrics(group, warmup_steps=warmup_steps)
-    sweep.rollout(env, policy, obs, steps, commands)
-    base.stop_metrics()
-    base.stop_reward_metrics()
-    if not sweep.commands_held(env, commands):
-        raise RuntimeError("run_reward_sweep: an environment left its grid cell's commands during the rollout")
-    scalar = base.read_metrics()
-    groups = scalar.pop("groups")
-    res = base.read_reward_metrics()
+    base, _, scalar, groups, res = sweep.run_beside_scalar("run_reward_sweep", "reward", policy, preset, cells, num_envs, steps, warmup_steps, seed, terrain)
     out = dict(preset=preset, cells=cells, names=res["names"], scales=res["scales"], terms=res["terms"], share=res["share"],
                reward_groups=res["groups"], metrics=scalar, groups=groups, num_envs=num_envs, steps=steps, warmup_steps=warmup_steps, seed=seed,
                dt=float(base.dt))
     out.update({row: res[row] for row in EXTRA_ROWS})
     return out
-
-
-def _number(x, fmt):
-    return format(x, fmt) if np.isfinite(x) else "–"
 
 
 def forgiven(result):
@@ -62,12 +45,12 @@ def reward_table(result):
         row = [name, f"{float(result['scales'][k]):.3g}"]
         for g in range(len(cells)):
             share = result["share"][name][g]
-            row.append(f"{_number(result['terms'][name][g][1], '.4g')} ({_number(100.0 * share, '+.1f')} %)")
+            row.append(f"{number(result['terms'][name][g][1], '.4g')} ({number(100.0 * share, '+.1f')} %)")
         lines.append("| " + " | ".join(row) + " |")
     for name in EXTRA_ROWS:
-        lines.append("| " + " | ".join([f"**{name}**", ""] + [_number(result[name][g][1], ".4g") for g in range(len(cells))]) + " |")
+        lines.append("| " + " | ".join([f"**{name}**", ""] + [number(result[name][g][1], ".4g") for g in range(len(cells))]) + " |")
     gone = forgiven(result)
-    lines.append("| " + " | ".join(["**forgiven by the clip**", ""] + [_number(gone[g], ".4g") for g in range(len(cells))]) + " |")
+    lines.append("| " + " | ".join(["**forgiven by the clip**", ""] + [number(gone[g], ".4g") for g in range(len(cells))]) + " |")
     for f, name in enumerate(GROUP_FIELDS[1:], start=1):
         lines.append("| " + " | ".join([f"{name} env-steps", ""] + [f"{result['reward_groups'][g][f]:.0f}" for g in range(len(cells))]) + " |")
     return "\n".join(lines)
@@ -75,11 +58,9 @@ def reward_table(result):
 
 def reward_to_json(result):
     """the JSON form of a run_reward_sweep result (NaN and infinities as null)"""
-    clean = lambda a: [clean(x) for x in a] if isinstance(a, list) else (a if np.isfinite(a) else None)
     table = lambda t: clean(np.asarray(t, np.float64).tolist())
     out = {k: result[k] for k in ("preset", "num_envs", "steps", "warmup_steps", "seed", "dt")}
-    out.update(cells=[dict(vx=c[0], yaw=c[1], gait=list(c[2])) for c in result["cells"]], fields=["count", "mean", "std", "min", "max", "nonfinite"],
-               group_fields=list(GROUP_FIELDS), names=list(result["names"]), scales=table(result["scales"]),
+    out.update(cells=sweep.cells_to_json(result["cells"]), fields=list(sweep.FIELDS), group_fields=list(GROUP_FIELDS), names=list(result["names"]), scales=table(result["scales"]),
                terms={n: table(t) for n, t in result["terms"].items()}, share={n: table(t) for n, t in result["share"].items()},
                reward_groups=table(result["reward_groups"]), forgiven=table(forgiven(result)))
     out.update({row: table(result[row]) for row in EXTRA_ROWS})

@@ -10,6 +10,7 @@ import numpy as np
 
 from . import sweep
 from .behaviour import COMMAND_INDEX
+from .sweep import clean, number
 
 SPECTRUM_ROWS = ["power", "peak_freq", "peak_share", "high_share", "centroid"]
 QUANTITIES = ["action", "torque", "dof_vel"]                                  # signals 0..11, 12..23, 24..35; joint j of leg j // 3
@@ -69,22 +70,9 @@ def run_spectrum_sweep(policy, preset, grid=None, num_envs=4096, steps=500, warm
     segments_dropped, "psd": (cells, 40, F) mean density, "psd_segments": (cells, 40), "freq": (F,), "signals", "high_bin", "metrics": the
     scalar table {name: (cells, 6)}, "groups": (cells, 5), "segment_steps", "high_freq", "taper", ...}."""
     cells = sweep.grid_cells(grid or sweep.DEFAULT_GRID)
-    env, _ = sweep.build_eval_env(preset, num_envs, seed, terrain)
-    if hasattr(policy, "eval"):
-        policy.eval()
-    base = env.env
-    obs, group, commands = sweep.prepare(env, cells)
+    base, _, scalar, groups, res = sweep.run_beside_scalar("run_spectrum_sweep", "spectrum", policy, preset, cells, num_envs, steps, warmup_steps, seed, terrain,
+                                                           dict(segment_steps=segment_steps, high_freq=high_freq, taper=taper))
     step_freq = [float(x) for x in sweep.command_table(cells, base.commands.shape[1], "cpu")[:, COMMAND_INDEX["frequency"]]]
-    base.start_metrics(group, warmup_steps=warmup_steps)
-    base.start_spectrum_metrics(group, warmup_steps=warmup_steps, segment_steps=segment_steps, high_freq=high_freq, taper=taper)
-    sweep.rollout(env, policy, obs, steps, commands)
-    base.stop_metrics()
-    base.stop_spectrum_metrics()
-    if not sweep.commands_held(env, commands):
-        raise RuntimeError("run_spectrum_sweep: an environment left its grid cell's commands during the rollout")
-    scalar = base.read_metrics()
-    groups = scalar.pop("groups")
-    res = base.read_spectrum_metrics()
     return dict(preset=preset, cells=cells, step_freq=step_freq, spectrum=res["metrics"], spectrum_groups=res["groups"], psd=res["psd"],
                 psd_segments=res["psd_segments"], freq=res["freq"], signals=res["signals"], high_bin=int(res["high_bin"]), metrics=scalar, groups=groups,
                 segment_steps=int(segment_steps), high_freq=float(high_freq), taper=taper, num_envs=num_envs, steps=steps, warmup_steps=warmup_steps,
@@ -106,10 +94,6 @@ def cell_summary(result, g):
     return out
 
 
-def _number(x, fmt):
-    return format(x, fmt) if np.isfinite(x) else "–"
-
-
 def spectrum_markdown_table(result):
     """per cell one row per quantity and joint type (the four legs averaged) and four trunk rows: the rms, the dominant frequency of the
     mean density, its share, the share at and above high_freq, the centroid, and the share locked to the commanded step frequency's
@@ -120,26 +104,17 @@ def spectrum_markdown_table(result):
     for g, cell in enumerate(result["cells"]):
         for row in cell_summary(result, g):
             lines.append("| " + " | ".join([f"{cell[0]:g}", f"{cell[1]:g}", f"{result['step_freq'][g]:g}", QUANTITY_LABELS.get(row["quantity"], row["quantity"]),
-                                            row["part"], _number(row["rms"], ".4g"), _number(row["peak_freq"], ".2f"), _number(row["peak_share"], ".3f"),
-                                            _number(row["high_share"], ".3f"), _number(row["centroid"], ".2f"), _number(row["gait_locked"], ".3f"),
+                                            row["part"], number(row["rms"], ".4g"), number(row["peak_freq"], ".2f"), number(row["peak_share"], ".3f"),
+                                            number(row["high_share"], ".3f"), number(row["centroid"], ".2f"), number(row["gait_locked"], ".3f"),
                                             f"{result['spectrum_groups'][g][3]:.0f}", f"{result['spectrum_groups'][g][4]:.0f}"]) + " |")
     return "\n".join(lines)
 
 
 def spectrum_to_json(result):
     """the JSON form of a run_spectrum_sweep result (NaN and infinities as null)"""
-    def clean(a):
-        if isinstance(a, dict):
-            return {k: clean(v) for k, v in a.items()}
-        if isinstance(a, (list, tuple)):
-            return [clean(x) for x in a]
-        if isinstance(a, (bool, str)):
-            return a
-        return a if np.isfinite(a) else None
     keep = ("preset", "num_envs", "steps", "warmup_steps", "seed", "dt", "segment_steps", "high_freq", "high_bin", "taper")
     out = {k: result[k] for k in keep}
-    out.update(cells=[dict(vx=c[0], yaw=c[1], gait=list(c[2]), step_freq=f) for c, f in zip(result["cells"], result["step_freq"])],
-               fields=["count", "mean", "std", "min", "max", "nonfinite"], group_fields=["envs", "steps", "resets", "segments", "segments_dropped"],
+    out.update(cells=sweep.cells_to_json(result["cells"], step_freq=result["step_freq"]), fields=list(sweep.FIELDS), group_fields=["envs", "steps", "resets", "segments", "segments_dropped"],
                signals=list(result["signals"]), freq=np.asarray(result["freq"], np.float64).tolist(),
                spectrum={m: clean(np.asarray(t).tolist()) for m, t in result["spectrum"].items()},
                spectrum_groups=np.asarray(result["spectrum_groups"]).tolist(), psd=clean(np.asarray(result["psd"]).tolist()),

@@ -106,6 +106,30 @@ def commands_held(env, commands):
     return bool(same.all())
 
 
+def run_beside_scalar(caller, family, policy, preset, cells, num_envs, steps, warmup_steps, seed, terrain, start_kwargs=None, prepare_cells=None,
+                      cell="grid cell"):
+    """The rollout every sweep with a table of its own shares: one environment for `preset`, environment i on cell i % cells (written by
+    prepare_cells(env, cells), default `prepare`), the scalar table and the table of `family` ("joint", "foot", ...: the stem of the
+    environment's start_ / stop_ / read_<family>_metrics hooks, the start taking `start_kwargs`) armed with the same groups and warm-up,
+    `steps` policy steps, both stopped, the commands checked (the RuntimeError names `caller` and the `cell`), both read.  Returns (the
+    base environment, group per environment, the scalar table without its "groups", those groups, what read_<family>_metrics gave)."""
+    env, _ = build_eval_env(preset, num_envs, seed, terrain)
+    if hasattr(policy, "eval"):
+        policy.eval()
+    base = env.env
+    obs, group, commands = (prepare_cells or prepare)(env, cells)
+    base.start_metrics(group, warmup_steps=warmup_steps)
+    getattr(base, f"start_{family}_metrics")(group, warmup_steps=warmup_steps, **(start_kwargs or {}))
+    rollout(env, policy, obs, steps, commands)
+    base.stop_metrics()
+    getattr(base, f"stop_{family}_metrics")()
+    if not commands_held(env, commands):
+        raise RuntimeError(f"{caller}: an environment left its {cell}'s commands during the rollout")
+    scalar = base.read_metrics()
+    groups = scalar.pop("groups")
+    return base, group, scalar, groups, getattr(base, f"read_{family}_metrics")()
+
+
 def run_sweep(policy, preset, grid=None, num_envs=4096, steps=500, warmup_steps=25, seed=1, terrain=None):
     """One table for one preset: {"preset", "cells": [(vx, yaw, gait)], "metrics": {name: (cells, 6) array of count, mean, std,
     min, max, nonfinite}, "groups": (cells, 5) array of envs, steps, episodes_terminated, episodes_timed_out, fall_rate}."""
@@ -122,6 +146,36 @@ def run_sweep(policy, preset, grid=None, num_envs=4096, steps=500, warmup_steps=
     res = env.env.read_metrics()
     groups = res.pop("groups")
     return dict(preset=preset, cells=cells, metrics=res, groups=groups, num_envs=num_envs, steps=steps, warmup_steps=warmup_steps, seed=seed)
+
+
+# ---- what every sweep's table and JSON share
+FIELDS = ["count", "mean", "std", "min", "max", "nonfinite"]                  # the columns of a metric table's row
+
+
+def number(x, fmt):
+    """x in the format `fmt`, a dash for a NaN or an infinity"""
+    return format(x, fmt) if np.isfinite(x) else "–"
+
+
+def mean_std(row):
+    """mean +- std of a metric table's row, a dash for a row that counted nothing"""
+    return f"{row[1]:.3g} ± {row[2]:.2g}" if row[0] > 0 else "–"
+
+
+def clean(a):
+    """nested dicts, lists and tuples of numbers, bools and strings as JSON takes them: NaN and infinities as None, tuples as lists"""
+    if isinstance(a, dict):
+        return {k: clean(v) for k, v in a.items()}
+    if isinstance(a, (list, tuple)):
+        return [clean(x) for x in a]
+    if isinstance(a, (bool, str)):
+        return a
+    return a if np.isfinite(a) else None
+
+
+def cells_to_json(cells, **more):
+    """the grid's cells (vx, yaw, gait) as a list of dicts; `more` = {key: one value per cell} adds entries to them"""
+    return [dict(vx=c[0], yaw=c[1], gait=list(c[2]), **{k: v[g] for k, v in more.items()}) for g, c in enumerate(cells)]
 
 
 def markdown_table(result, metrics=("lin_vel_rmsd", "ang_vel_rmsd", "base_height", "max_torques", "power_consumption", "CoT", "froude_number")):

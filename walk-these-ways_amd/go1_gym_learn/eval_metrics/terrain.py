@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import sweep
+from .sweep import number
 
 # the generator a tile of column choice `c` gets, in the order of the thresholds of go1_gym.utils.terrain.Terrain.make_terrain
 # (cumulative terrain_proportions p[0], p[1], ...): below p[0] / 2, below p[0], below p[1], ...
@@ -88,10 +89,6 @@ def run_terrain_sweep(policy, preset, vx=1.0, num_envs=4096, window=500, warmup=
                 tile=(float(t.terrain_length), float(t.terrain_width)), dt=float(base.dt))
 
 
-def _number(x, fmt):
-    return format(x, fmt) if np.isfinite(x) else "–"
-
-
 def terrain_markdown_grid(result):
     """rows = difficulty, columns = terrain type; a cell reads success rate / stumble rate / mean swing foot height [m] / fall rate:
     traversed over the decided environments, the share of measured steps with a stumble, the mean height of the swinging feet's
@@ -104,8 +101,8 @@ def terrain_markdown_grid(result):
         row = [f"{result['difficulty'][index[(level, 0)]]:.2f}"]
         for k in range(cols):
             g = index[(level, k)]
-            row.append(" / ".join([_number(result["groups"][g, 5], ".2f"), _number(result["metrics"]["stumble"][g, 1], ".3f"),
-                                   _number(result["metrics"]["swing_foot_height"][g, 1], ".3f"), _number(result["outcomes"]["fell"][g, 1], ".2f")]))
+            row.append(" / ".join([number(result["groups"][g, 5], ".2f"), number(result["metrics"]["stumble"][g, 1], ".3f"),
+                                   number(result["metrics"]["swing_foot_height"][g, 1], ".3f"), number(result["outcomes"]["fell"][g, 1], ".2f")]))
         lines.append("| " + " | ".join(row) + " |")
     return "\n".join(lines)
 
@@ -114,7 +111,7 @@ def terrain_to_json(result):
     """the JSON form of a run_terrain_sweep result (without the per-environment arrays)"""
     keep = ("preset", "vx", "num_envs", "window", "warmup", "seed", "num_rows", "num_cols", "mesh_type", "dt")
     out = {k: result[k] for k in keep}
-    out.update(tile=list(result["tile"]), fields=["count", "mean", "std", "min", "max", "nonfinite"],
+    out.update(tile=list(result["tile"]), fields=list(sweep.FIELDS),
                group_fields=["envs", "running", "traversed", "fell", "timed_out", "success_rate"],
                cells=[dict(level=lv, type=k, terrain_type=name, difficulty=d)
                       for (lv, k), name, d in zip(result["cells"], result["terrain_type"], result["difficulty"])],

@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import sweep
+from .sweep import clean, number
 
 TRUNK_TERMS = ["roll_sin", "pitch_sin", "tilt", "roll_rate", "pitch_rate", "vertical_vel", "orientation", "lin_vel_z", "ang_vel_xy"]
 TRUNK_METRICS = ["roll_sin", "pitch_sin", "tilt", "tilt_exceeded", "roll_rate", "pitch_rate", "vertical_vel", "accel_horizontal", "accel_vertical",
@@ -37,28 +38,11 @@ def run_trunk_sweep(policy, preset, grid=None, num_envs=4096, steps=500, warmup_
     (cells, 4) array of envs, steps, resets, segments_dropped, "tilt_hist": (cells, 16), "tilt_edges": (17,), "metrics": the scalar table
     {name: (cells, 6)}, "groups": (cells, 5), "segment_steps", "tilt_limit", ...}."""
     cells = sweep.grid_cells(grid or sweep.DEFAULT_GRID)
-    env, _ = sweep.build_eval_env(preset, num_envs, seed, terrain)
-    if hasattr(policy, "eval"):
-        policy.eval()
-    base = env.env
-    obs, group, commands = sweep.prepare(env, cells)
-    base.start_metrics(group, warmup_steps=warmup_steps)
-    base.start_trunk_metrics(group, warmup_steps=warmup_steps, segment_steps=segment_steps, tilt_limit=tilt_limit)
-    sweep.rollout(env, policy, obs, steps, commands)
-    base.stop_metrics()
-    base.stop_trunk_metrics()
-    if not sweep.commands_held(env, commands):
-        raise RuntimeError("run_trunk_sweep: an environment left its grid cell's commands during the rollout")
-    scalar = base.read_metrics()
-    groups = scalar.pop("groups")
-    res = base.read_trunk_metrics()
+    base, _, scalar, groups, res = sweep.run_beside_scalar("run_trunk_sweep", "trunk", policy, preset, cells, num_envs, steps, warmup_steps, seed, terrain,
+                                                           dict(segment_steps=segment_steps, tilt_limit=tilt_limit))
     return dict(preset=preset, cells=cells, trunk=res["metrics"], trunk_groups=res["groups"], tilt_hist=res["tilt_hist"], tilt_edges=res["tilt_edges"],
                 metrics=scalar, groups=groups, segment_steps=int(segment_steps), tilt_limit=float(tilt_limit), num_envs=num_envs, steps=steps,
                 warmup_steps=warmup_steps, seed=seed, dt=float(base.dt))
-
-
-def _number(x, fmt):
-    return format(x, fmt) if np.isfinite(x) else "–"
 
 
 def _rms(row):
@@ -84,24 +68,22 @@ def trunk_markdown_table(result):
     for g, cell in enumerate(result["cells"]):
         at = lambda name: np.asarray(t[name][g], np.float64)
         peak_v = max(abs(at("accel_vertical")[3]), abs(at("accel_vertical")[4])) if at("accel_vertical")[0] > 0 else float("nan")
-        row = [f"{cell[0]:g}", f"{cell[1]:g}", _number(_degrees(at("tilt")[1]), ".2f"), _number(_degrees(at("tilt")[4]), ".2f"),
-               _number(at("tilt_exceeded")[1], ".4f"), _number(_rms(at("roll_rate")), ".3f"), _number(_rms(at("pitch_rate")), ".3f"),
-               _number(_rms(at("vertical_vel")), ".3f"), _number(_rms(at("accel_horizontal")) / GRAVITY, ".3f"),
-               _number(at("accel_horizontal")[4] / GRAVITY, ".3f"), _number(_rms(at("accel_vertical")) / GRAVITY, ".3f"), _number(peak_v / GRAVITY, ".3f"),
-               _number(at("support_feet")[1], ".2f"), _number(at("support_margin")[1], ".4f"), _number(at("margin_negative")[1], ".4f"),
-               _number(at("support_line_dist")[1], ".4f"), _number(at("lateral_drift")[1], ".4f"), _number(_degrees(at("heading_drift")[1]), ".2f"),
-               _number(at("progress_err")[1], ".4f"), f"{at('lateral_drift')[0] + at('lateral_drift')[5]:.0f}", f"{result['trunk_groups'][g][3]:.0f}"]
+        row = [f"{cell[0]:g}", f"{cell[1]:g}", number(_degrees(at("tilt")[1]), ".2f"), number(_degrees(at("tilt")[4]), ".2f"),
+               number(at("tilt_exceeded")[1], ".4f"), number(_rms(at("roll_rate")), ".3f"), number(_rms(at("pitch_rate")), ".3f"),
+               number(_rms(at("vertical_vel")), ".3f"), number(_rms(at("accel_horizontal")) / GRAVITY, ".3f"),
+               number(at("accel_horizontal")[4] / GRAVITY, ".3f"), number(_rms(at("accel_vertical")) / GRAVITY, ".3f"), number(peak_v / GRAVITY, ".3f"),
+               number(at("support_feet")[1], ".2f"), number(at("support_margin")[1], ".4f"), number(at("margin_negative")[1], ".4f"),
+               number(at("support_line_dist")[1], ".4f"), number(at("lateral_drift")[1], ".4f"), number(_degrees(at("heading_drift")[1]), ".2f"),
+               number(at("progress_err")[1], ".4f"), f"{at('lateral_drift')[0] + at('lateral_drift')[5]:.0f}", f"{result['trunk_groups'][g][3]:.0f}"]
         lines.append("| " + " | ".join(row) + " |")
     return "\n".join(lines)
 
 
 def trunk_to_json(result):
     """the JSON form of a run_trunk_sweep result (NaN and infinities as null)"""
-    clean = lambda a: [clean(x) for x in a] if isinstance(a, list) else (a if np.isfinite(a) else None)
     keep = ("preset", "num_envs", "steps", "warmup_steps", "seed", "dt", "segment_steps", "tilt_limit")
     out = {k: result[k] for k in keep}
-    out.update(cells=[dict(vx=c[0], yaw=c[1], gait=list(c[2])) for c in result["cells"]], fields=["count", "mean", "std", "min", "max", "nonfinite"],
-               group_fields=["envs", "steps", "resets", "segments_dropped"], trunk={m: clean(np.asarray(t).tolist()) for m, t in result["trunk"].items()},
+    out.update(cells=sweep.cells_to_json(result["cells"]), fields=list(sweep.FIELDS), group_fields=["envs", "steps", "resets", "segments_dropped"], trunk={m: clean(np.asarray(t).tolist()) for m, t in result["trunk"].items()},
                trunk_groups=np.asarray(result["trunk_groups"]).tolist(), tilt_hist=np.asarray(result["tilt_hist"]).tolist(),
                tilt_edges=clean(np.asarray(result["tilt_edges"]).tolist()))
     return out
