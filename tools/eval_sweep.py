@@ -95,6 +95,16 @@ include/go1place.h): per foot where it touches down against its nominal stance p
 mean error in stance and in swing, the stance sweep, the stride length against |v| / f, the track width against the commanded one, and
 an 8 x 8 footprint map of `--map-cell` metres per cell (default 0.03, a placeholder).  `<out>/eval/<preset>_placement.json` and the
 footprint figure `<preset>_footprints.png` are written and the table is printed and appended to `<preset>_placement.md`.
+
+    python tools/eval_sweep.py --checkpoint RUN_DIR/checkpoints --out RUN_DIR --episodes --steps 1500 --vx 0.5 1.0 1.5
+
+With `--episodes` the velocity grid is swept with the episode table armed beside the scalar one, both before the reset that starts the
+rollout (go1_gym_learn.eval_metrics.episodes, include/go1episode.h): per cell the episodes closed, still open and cut, the share that
+fell, return, length, time to a fall, reward per step, the return discounted with `--gamma` (default 0.99), displacement, path length, the
+two tracking errors over an episode, and the Kaplan-Meier survival estimate over sixteen length bins of `--bin-steps` steps (default 0:
+ceil(steps / 16)), the episodes still open at the end counted as censored.  `--steps 1500` lets every environment finish an episode of
+the 20 s configuration.  `<out>/eval/<preset>_episodes.json` and the survival figure `<preset>_survival.png` are written and the table
+is printed and appended to `<preset>_episodes.md`.
 Run on the GPU box."""
 import argparse
 import functools
@@ -200,6 +210,9 @@ MODES = (
     Mode("--placement", "placement", "run_placement_sweep", "placement_to_json", "placement_table", "plot_footprints", "_placement", "_footprints.png",
          "axes {grid}, foot placement", options=dict(map_cell=0.03), axes=True,
          check=lambda a: not 0.0 < a.map_cell < float("inf") and "--map-cell has to be a positive length"),
+    Mode("--episodes", "episodes", "run_episode_sweep", "episode_to_json", "episode_markdown_table", "plot_survival", "_episodes", "_survival.png",
+         "vx {a.vx}, whole episodes (gamma {a.gamma})", options=dict(gamma=0.99, bin_steps=0),
+         check=lambda a: (not 0.0 < a.gamma <= 1.0 or a.bin_steps < 0) and "--gamma has to lie in (0, 1] and --bin-steps must not be negative (0: steps / 16)"),
 )
 MODE = {mode.dest: mode for mode in MODES}
 
@@ -250,6 +263,9 @@ def parse_args(argv=None):
     ap.add_argument("--rewards", action="store_true", help="break the step reward down by term over the velocity grid, beside the scalar table")
     ap.add_argument("--placement", action="store_true", help="measure foot placement and stride geometry over the --axis product, beside the scalar table")
     ap.add_argument("--map-cell", type=float, default=None, help="with --placement: the side of a cell of the footprint map in metres, default 0.03")
+    ap.add_argument("--episodes", action="store_true", help="measure whole episodes (return, length, survival) over the velocity grid, beside the scalar table")
+    ap.add_argument("--gamma", type=float, default=None, help="with --episodes: the discount of the discounted return, in (0, 1], default 0.99")
+    ap.add_argument("--bin-steps", type=int, default=None, help="with --episodes: the width of a length bin in steps, default 0: ceil(steps / 16)")
     ap.add_argument("--out", required=True)
     a = ap.parse_args(argv)
     a.tiles = a.terrain == "tiles"
@@ -393,6 +409,7 @@ run_rewards = functools.partial(run_mode, MODE["rewards"])
 run_gait = functools.partial(run_mode, MODE["coordination"])
 run_spectrum = functools.partial(run_mode, MODE["spectrum"])
 run_placement = functools.partial(run_mode, MODE["placement"])              # (its grid is the --axis product)
+run_episodes = functools.partial(run_mode, MODE["episodes"])
 
 
 def behaviour_axes(a):

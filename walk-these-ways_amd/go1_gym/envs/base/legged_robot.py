@@ -151,10 +151,16 @@ class LeggedRobot(BaseTask):
                  ("spectrum", "_spectrum", "go1spectrum_host", "Go1Spectrum", "accumulate"),
                  ("placement", "_place", "go1place_host", "Go1Place", "accumulate"),
                  ("rewards", "_reward", "go1reward_host", "Go1Reward", None))
+    # The families that came after those eleven, in the same five columns.  They are a table of their own because the eleven rows above, the
+    # stepped order and _STATE_FAMILIES made of them are pinned as they are (tests/test_family_wiring.py): a row here is launched after
+    # the reward family's, in this order, and load_state() names it after the eleven and before the camera.
+    _LATER_FAMILIES = (("episodes", "_episodes", "go1episode_host", "Go1Episodes", "accumulate"),)
     _STEPPED = tuple((attr, method) for _, attr, _, _, method in _FAMILIES if method)
+    _STEPPED_LATER = tuple((attr, method) for _, attr, _, _, method in _LATER_FAMILIES if method)
     # load_state() is refused while one of them is armed: their accumulators are not part of a saved state
     _STATE_FAMILIES = tuple((name, attr) for name, attr, _, _, _ in _FAMILIES)
-    _HOST = {attr: (module, cls) for _, attr, module, cls, _ in _FAMILIES}
+    _LATER_STATE_FAMILIES = tuple((name, attr) for name, attr, _, _, _ in _LATER_FAMILIES)
+    _HOST = {attr: (module, cls) for _, attr, module, cls, _ in _FAMILIES + _LATER_FAMILIES}
     _HOST["_push"] = ("go1eval_host", "Go1Push")          # made by the first push_robots(); neither stepped nor a state family
 
     def __init__(self, cfg, sim_params, physics_engine, sim_device, headless, eval_cfg=None,
@@ -168,7 +174,7 @@ class LeggedRobot(BaseTask):
         self.initial_dynamics_dict = initial_dynamics_dict
         self._render = None               # go1render_host.Go1Render, created by the first start_recording() / render()
         self._frames = [[], []]           # per camera: the last complete recording handed out
-        for attr in self._HOST:           # _metrics ... _reward and _push: each made by the first start_*() / push_robots() of its family
+        for attr in self._HOST:           # _metrics ... _reward, _episodes and _push: each made by the first start_*() / push_robots() of its family
             setattr(self, attr, None)
         self._state = None                # go1state_host.Go1State, created by the first save_state() / load_state()
         if eval_cfg is not None:          # reference legged_robot.py:41-42
@@ -469,6 +475,10 @@ class LeggedRobot(BaseTask):
                     self._behaviour.accumulate()
         if self._reward is not None and self._reward.armed:
             self._reward.accumulate(H.gravity_at(self.sim_config, self.common_step_counter))     # (the gravity of the step just taken)
+        for attr, method in self._STEPPED_LATER:
+            family = getattr(self, attr)
+            if family is not None and family.armed:
+                getattr(family, method)()
         if self._curriculum_sync and (self.common_step_counter + 1) % self.sim_config.curriculum_update_interval == 0:
             # ONE exchange for the last `curriculum_update_interval` steps' success counts (a slot per step), then the per-step
             # updates in order: every rank applies what a single process over the concatenated shards would
@@ -892,6 +902,28 @@ class LeggedRobot(BaseTask):
         per-environment state}: one reduction launch and the device-to-host copies"""
         return self._started("read_reward_metrics", "_reward", "start_reward_metrics").read()
 
+    # ---- whole episodes (include/go1episode.h, libgo1episode.so: a library of its own): the state of every environment's open episode is
+    # carried on the device from step to step, and at its close eleven values are folded (length, whether it fell, return, reward per step,
+    # discounted return, displacement, path length, the two tracking errors over the episode) and its length enters the histogram of the
+    # falls or of the time-outs; the episodes still open at the read are binned by their age: the censored observations of a survival
+    # curve.  One more launch per step while it is armed, after the reward family's; independent of the other measurements.
+    def start_episode_metrics(self, groups, warmup_steps=0, gamma=0.99, bin_steps=63):
+        """begin an episode measurement: `groups` = one int per environment (the row of the result tables it counts towards, -1 = not
+        evaluated); steps with episode_length_buf <= warmup_steps enter no tracking error (returns and lengths count every step).  gamma:
+        the discount of discounted_return, in (0, 1]; bin_steps: the width of a length bin (63 puts the 1001 steps of a 20 s episode into
+        the sixteen bins).  Started before reset(), every environment's first episode is seen whole"""
+        self._family("start_episode_metrics", "_episodes").arm(groups, warmup_steps, gamma=gamma, bin_steps=bin_steps)
+
+    def stop_episode_metrics(self):
+        """stop folding steps; what was measured stays readable"""
+        self._disarm("stop_episode_metrics", "_episodes")
+
+    def read_episode_metrics(self):
+        """go1episode_host.Go1Episodes.read(): {"metrics": {name: (groups, 6)}, "groups": (groups, 9) array of envs, steps, closed, fell,
+        timed_out, open, cut, unseen, open_steps, "fall_hist", "timeout_hist", "open_hist": (groups, 16), "bin_edges": (17,) in steps,
+        "gamma", "bin_steps", and the per-environment state}: one reduction launch and the device-to-host copies"""
+        return self._started("read_episode_metrics", "_episodes", "start_episode_metrics").read()
+
     def last_reward_terms(self):
         """((K + 4, N) scaled terms, sum, positive, negative and total of the last accumulated step, (N,) valid): views, no copy"""
         return self._started("last_reward_terms", "_reward", "start_reward_metrics").last()
@@ -933,7 +965,7 @@ class LeggedRobot(BaseTask):
         branched environment's draws after the load are those of its own index.  Refused while a measurement family, a trace or a
         camera is armed: their accumulators are not part of the state, and a restore is a teleport to them."""
         stater = self._stater("load_state")
-        armed = [name for name, attr in self._STATE_FAMILIES if getattr(self, attr) is not None and getattr(self, attr).armed]
+        armed = [name for name, attr in self._STATE_FAMILIES + self._LATER_STATE_FAMILIES if getattr(self, attr) is not None and getattr(self, attr).armed]
         if self._render is not None and self._render.any_armed:
             armed.append("camera")
         if armed:

@@ -10,4 +10,6 @@ include/go1feet.h), `trunk` what the trunk does: tilt, accelerations, support ma
 `plot_gait`; include/go1gait.h), `spectrum` where in frequency the actions, torques, joint speeds and trunk rates carry their energy
 (`run_spectrum_sweep`, `gait_locked`, `plot_spectrum`; include/go1spectrum.h), `placement` where every foot lands against its nominal stance
 point and the Raibert heuristic's target, and the stride length and track width the robot realises (`placement_errors`, `run_placement_sweep`,
-`plot_footprints`; include/go1place.h)."""
+`plot_footprints`; include/go1place.h), `episodes` what whole episodes come to: return, length, time to a fall, distance and the survival
+curve with the episodes still open as censored observations (`run_episode_sweep`, `kaplan_meier`, `episode_to_json`,
+`episode_markdown_table`, `plot_survival`; include/go1episode.h)."""
