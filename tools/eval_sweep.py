@@ -105,6 +105,17 @@ two tracking errors over an episode, and the Kaplan-Meier survival estimate over
 ceil(steps / 16)), the episodes still open at the end counted as censored.  `--steps 1500` lets every environment finish an episode of
 the 20 s configuration.  `<out>/eval/<preset>_episodes.json` and the survival figure `<preset>_survival.png` are written and the table
 is printed and appended to `<preset>_episodes.md`.
+
+    python tools/eval_sweep.py --checkpoint RUN_DIR/checkpoints --out RUN_DIR --sensitivity --presets rand_large --pair friction motor_strength
+
+With `--sensitivity` the velocity grid is swept with the sensitivity table armed beside the scalar one
+(go1_gym_learn.eval_metrics.sensitivity, include/go1sens.h): per cell and per dynamics parameter the preset randomises (friction,
+restitution, payload, com_x, com_y, com_z, motor_strength; Kp_factor and Kd_factor when asked for) sixteen bins of its value with the
+exposure, the falls charged to the value that was in force, the tracking errors and the power.  `--parameters NAME ...` chooses the
+parameters reported, `--pair A B` adds the 8 x 8 hazard map over two of them, `--min-exposure K` (default 200, a placeholder) is the
+number of steps a bin needs before it enters an effect.  `<out>/eval/<preset>_sensitivity.json` and the figure
+`<preset>_sensitivity.png` are written and the table, with the ranking of the parameters below it, is printed and appended to
+`<preset>_sensitivity.md`.
 Run on the GPU box."""
 import argparse
 import functools
@@ -189,6 +200,16 @@ def _joint_envelope(res):
                              soft_vel_limit=res["soft_vel_limit"])
 
 
+def _check_sensitivity(a):
+    from go1_gym_learn.eval_metrics.sensitivity import PARAMETERS
+    unknown = [name for name in (a.parameters or []) + (a.pair or []) if name not in PARAMETERS]
+    if unknown:
+        return f"--parameters and --pair take names of {PARAMETERS}, not {unknown[0]}"
+    if a.pair and a.pair[0] == a.pair[1]:
+        return "--pair takes two different parameters"
+    return a.min_exposure < 1 and "--min-exposure has to be at least 1"
+
+
 MODES = (
     Mode("--joints", "joints", "run_joint_sweep", "joint_to_json", "joint_markdown_table", "plot_envelope", "_joints", "_envelope.png",
          "vx {a.vx}, per-joint actuator usage", figure_input=_joint_envelope),
@@ -213,6 +234,9 @@ MODES = (
     Mode("--episodes", "episodes", "run_episode_sweep", "episode_to_json", "episode_markdown_table", "plot_survival", "_episodes", "_survival.png",
          "vx {a.vx}, whole episodes (gamma {a.gamma})", options=dict(gamma=0.99, bin_steps=0),
          check=lambda a: (not 0.0 < a.gamma <= 1.0 or a.bin_steps < 0) and "--gamma has to lie in (0, 1] and --bin-steps must not be negative (0: steps / 16)"),
+    Mode("--sensitivity", "sensitivity", "run_sensitivity_sweep", "sensitivity_to_json", "sensitivity_markdown_table", "plot_sensitivity", "_sensitivity",
+         "_sensitivity.png", "vx {a.vx}, robustness against the randomised dynamics", options=dict(parameters=None, pair=None, min_exposure=200),
+         check=_check_sensitivity),
 )
 MODE = {mode.dest: mode for mode in MODES}
 
@@ -266,6 +290,10 @@ def parse_args(argv=None):
     ap.add_argument("--episodes", action="store_true", help="measure whole episodes (return, length, survival) over the velocity grid, beside the scalar table")
     ap.add_argument("--gamma", type=float, default=None, help="with --episodes: the discount of the discounted return, in (0, 1], default 0.99")
     ap.add_argument("--bin-steps", type=int, default=None, help="with --episodes: the width of a length bin in steps, default 0: ceil(steps / 16)")
+    ap.add_argument("--sensitivity", action="store_true", help="measure exposure, falls and tracking per bin of the randomised dynamics parameters, beside the scalar table")
+    ap.add_argument("--parameters", nargs="+", default=None, metavar="NAME", help="with --sensitivity: the parameters reported, default: those the preset randomises")
+    ap.add_argument("--pair", nargs=2, default=None, metavar=("A", "B"), help="with --sensitivity: two parameters for the 8 x 8 hazard map")
+    ap.add_argument("--min-exposure", type=int, default=None, help="with --sensitivity: steps a bin needs before it enters an effect, default 200 (a placeholder)")
     ap.add_argument("--out", required=True)
     a = ap.parse_args(argv)
     a.tiles = a.terrain == "tiles"
@@ -410,6 +438,7 @@ run_gait = functools.partial(run_mode, MODE["coordination"])
 run_spectrum = functools.partial(run_mode, MODE["spectrum"])
 run_placement = functools.partial(run_mode, MODE["placement"])              # (its grid is the --axis product)
 run_episodes = functools.partial(run_mode, MODE["episodes"])
+run_sensitivity = functools.partial(run_mode, MODE["sensitivity"])
 
 
 def behaviour_axes(a):

@@ -155,12 +155,18 @@ class LeggedRobot(BaseTask):
     # stepped order and _STATE_FAMILIES made of them are pinned as they are (tests/test_family_wiring.py): a row here is launched after
     # the reward family's, in this order, and load_state() names it after the eleven and before the camera.
     _LATER_FAMILIES = (("episodes", "_episodes", "go1episode_host", "Go1Episodes", "accumulate"),)
+    # The families after the episode family, in the same five columns: the two tables above and the tuples made of them are pinned as they
+    # are (tests/test_family_wiring.py, tests/test_episode_metrics.py), so further rows go here: launched after the later families', in
+    # this order, and named by load_state() after them and before the camera.
+    _MORE_FAMILIES = (("sensitivity", "_sens", "go1sens_host", "Go1Sensitivity", "accumulate"),)
     _STEPPED = tuple((attr, method) for _, attr, _, _, method in _FAMILIES if method)
     _STEPPED_LATER = tuple((attr, method) for _, attr, _, _, method in _LATER_FAMILIES if method)
+    _STEPPED_MORE = tuple((attr, method) for _, attr, _, _, method in _MORE_FAMILIES if method)
     # load_state() is refused while one of them is armed: their accumulators are not part of a saved state
     _STATE_FAMILIES = tuple((name, attr) for name, attr, _, _, _ in _FAMILIES)
     _LATER_STATE_FAMILIES = tuple((name, attr) for name, attr, _, _, _ in _LATER_FAMILIES)
-    _HOST = {attr: (module, cls) for _, attr, module, cls, _ in _FAMILIES + _LATER_FAMILIES}
+    _MORE_STATE_FAMILIES = tuple((name, attr) for name, attr, _, _, _ in _MORE_FAMILIES)
+    _HOST = {attr: (module, cls) for _, attr, module, cls, _ in _FAMILIES + _LATER_FAMILIES + _MORE_FAMILIES}
     _HOST["_push"] = ("go1eval_host", "Go1Push")          # made by the first push_robots(); neither stepped nor a state family
 
     def __init__(self, cfg, sim_params, physics_engine, sim_device, headless, eval_cfg=None,
@@ -174,7 +180,7 @@ class LeggedRobot(BaseTask):
         self.initial_dynamics_dict = initial_dynamics_dict
         self._render = None               # go1render_host.Go1Render, created by the first start_recording() / render()
         self._frames = [[], []]           # per camera: the last complete recording handed out
-        for attr in self._HOST:           # _metrics ... _reward, _episodes and _push: each made by the first start_*() / push_robots() of its family
+        for attr in self._HOST:           # _metrics ... _reward, _episodes, _sens and _push: each made by the first start_*() / push_robots() of its family
             setattr(self, attr, None)
         self._state = None                # go1state_host.Go1State, created by the first save_state() / load_state()
         if eval_cfg is not None:          # reference legged_robot.py:41-42
@@ -475,7 +481,7 @@ class LeggedRobot(BaseTask):
                     self._behaviour.accumulate()
         if self._reward is not None and self._reward.armed:
             self._reward.accumulate(H.gravity_at(self.sim_config, self.common_step_counter))     # (the gravity of the step just taken)
-        for attr, method in self._STEPPED_LATER:
+        for attr, method in self._STEPPED_LATER + self._STEPPED_MORE:
             family = getattr(self, attr)
             if family is not None and family.armed:
                 getattr(family, method)()
@@ -516,6 +522,8 @@ class LeggedRobot(BaseTask):
             self._render.note_reset(None if full else env_ids)
         if self._reward is not None and self._reward.armed:         # the reset cleared histories the reward family keeps a snapshot of
             self._reward.snapshot()
+        if self._sens is not None and self._sens.armed:             # the reset re-drew the motor parameters: what is in force from now
+            self._sens.snapshot()
 
     def set_idx_pose(self, env_ids, dof_pos, base_state):
         """reference legged_robot.py:241-261: the buffers ARE the simulator state, so writing them is the push."""
@@ -924,6 +932,32 @@ class LeggedRobot(BaseTask):
         "gamma", "bin_steps", and the per-environment state}: one reduction launch and the device-to-host copies"""
         return self._started("read_episode_metrics", "_episodes", "start_episode_metrics").read()
 
+    # ---- robustness against the randomised dynamics (include/go1sens.h, libgo1sens.so: a library of its own): the values of the nine
+    # dynamics parameters in force are carried on the device from step to step (the step kernel re-draws them at resets and at the
+    # randomisation interval, and on the step of a fall the buffers already hold the respawned robot's), and every step's exposure, fall
+    # or time-out, reward, tracking errors and power are charged to the bin of the value that was in force.  One more launch per step
+    # while it is armed, after the episode family's; independent of the other measurements.
+    def start_sensitivity_metrics(self, groups, warmup_steps=0, ranges=None, pair=None):
+        """begin a sensitivity measurement: `groups` = one int per environment (the row of the result tables it counts towards, -1 = not
+        evaluated); steps with episode_length_buf <= warmup_steps enter no tracking error and no power (exposure, falls and rewards count
+        every step).  The parameters whose randomize_* switch is on are measured over the configuration's range in sixteen bins;
+        ranges = {name: (lo, hi)} replaces a range or adds a parameter (names: go1sens_host.PARAMETERS; None for the span: the
+        configuration's range of a parameter whose switch is off).  pair = (name, name): also an
+        8 x 8 map over two measured parameters"""
+        family = self._family("start_sensitivity_metrics", "_sens")
+        family.arm(groups, warmup_steps, ranges=family.ranges_of(self.cfg.domain_rand, ranges), pair=pair)
+
+    def stop_sensitivity_metrics(self):
+        """stop folding steps; what was measured stays readable"""
+        self._disarm("stop_sensitivity_metrics", "_sens")
+
+    def read_sensitivity_metrics(self):
+        """go1sens_host.Go1Sensitivity.read(): {"parameters", "active", "edges": (9, 17), "value": {name: (groups, 6)}, "curves":
+        {quantity: (groups, 9, 16)} of steps, measured, falls, timeouts and the sums of reward, the two tracking errors and power,
+        "counts": (groups, 9, 3) unbinned, redraws, bad, "groups": (groups, 2) environments and launches, "pair", "pair_map":
+        (groups, 4, 8, 8) or None, and the per-environment state}: one reduction launch and the device-to-host copies"""
+        return self._started("read_sensitivity_metrics", "_sens", "start_sensitivity_metrics").read()
+
     def last_reward_terms(self):
         """((K + 4, N) scaled terms, sum, positive, negative and total of the last accumulated step, (N,) valid): views, no copy"""
         return self._started("last_reward_terms", "_reward", "start_reward_metrics").last()
@@ -965,7 +999,7 @@ class LeggedRobot(BaseTask):
         branched environment's draws after the load are those of its own index.  Refused while a measurement family, a trace or a
         camera is armed: their accumulators are not part of the state, and a restore is a teleport to them."""
         stater = self._stater("load_state")
-        armed = [name for name, attr in self._STATE_FAMILIES + self._LATER_STATE_FAMILIES if getattr(self, attr) is not None and getattr(self, attr).armed]
+        armed = [name for name, attr in self._STATE_FAMILIES + self._LATER_STATE_FAMILIES + self._MORE_STATE_FAMILIES if getattr(self, attr) is not None and getattr(self, attr).armed]
         if self._render is not None and self._render.any_armed:
             armed.append("camera")
         if armed:

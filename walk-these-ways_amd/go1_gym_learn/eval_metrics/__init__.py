@@ -12,4 +12,6 @@ include/go1feet.h), `trunk` what the trunk does: tilt, accelerations, support ma
 point and the Raibert heuristic's target, and the stride length and track width the robot realises (`placement_errors`, `run_placement_sweep`,
 `plot_footprints`; include/go1place.h), `episodes` what whole episodes come to: return, length, time to a fall, distance and the survival
 curve with the episodes still open as censored observations (`run_episode_sweep`, `kaplan_meier`, `episode_to_json`,
-`episode_markdown_table`, `plot_survival`; include/go1episode.h)."""
+`episode_markdown_table`, `plot_survival`; include/go1episode.h), `sensitivity` how a policy holds up as the randomised dynamics move:
+exposure, falls, tracking errors and power per bin of friction, restitution, payload, centre-of-mass displacement and motor strength
+(`run_sensitivity_sweep`, `hazard`, `wilson`, `effect`, `rank_parameters`, `plot_sensitivity`; include/go1sens.h)."""

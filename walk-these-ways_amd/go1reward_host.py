@@ -15,6 +15,7 @@ import torch
 
 import go1sim_abi as abi
 from go1eval_host import _ACCUMULATORS, FIELD_NAMES, _Table
+from go1sim_host import release
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libgo1reward.so")
@@ -170,7 +171,7 @@ class Go1Reward(_Table):
     def __del__(self):
         try:
             if self.handle:
-                self.lib.go1reward_destroy(self.handle)
+                release(self.lib.go1reward_destroy, self.handle)       # (not inside a stream capture: go1sim_host.release)
                 self.handle = None
         except Exception:
             pass

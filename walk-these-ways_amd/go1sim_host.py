@@ -773,7 +773,24 @@ class Go1Sim:
     def __del__(self):
         try:
             if self.handle:
-                self.lib.go1sim_destroy(self.handle)
+                release(self.lib.go1sim_destroy, self.handle)
                 self.handle = None
         except Exception:
             pass
+
+
+_PUT_OFF = []          # (destroy, handle) of native objects released while the releasing thread's stream was being captured
+
+
+def release(destroy, handle):
+    """destroy(handle) of a native object that owns device memory (its destroy calls hipFree), but not while the current stream is being
+    captured: a hipFree there invalidates the capture, and a __del__ runs wherever the garbage collector happens to run (an environment
+    is part of reference cycles, so it is the collector that releases it).  What was put off is destroyed by the next release outside
+    a capture."""
+    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        _PUT_OFF.append((destroy, handle))
+        return
+    while _PUT_OFF:
+        put_off, h = _PUT_OFF.pop()
+        put_off(h)
+    destroy(handle)
