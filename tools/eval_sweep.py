@@ -116,6 +116,19 @@ parameters reported, `--pair A B` adds the 8 x 8 hazard map over two of them, `-
 number of steps a bin needs before it enters an effect.  `<out>/eval/<preset>_sensitivity.json` and the figure
 `<preset>_sensitivity.png` are written and the table, with the ranking of the parameters below it, is printed and appended to
 `<preset>_sensitivity.md`.
+
+    python tools/eval_sweep.py --checkpoint RUN_DIR/checkpoints --out RUN_DIR --observations --presets rand_large --against RUN_DIR/eval/static_medium_observations.json
+
+With `--observations` the velocity grid is swept with the observation table armed beside the scalar one
+(go1_gym_learn.eval_metrics.observations, include/go1obs.h): per cell and per column of obs_buf (and of privileged_obs_buf unless
+`--no-privileged`) the moments, sixteen bins and two tails over the channel's range (placeholders by kind unless `--against` gives
+them), the steps at the observation clip and the step-to-step change.  `--against FILE.json` takes an earlier run's
+`<preset>_observations.json` or a profile written from `observations.profile_from_array` (a robot log's observations): its bin edges
+become this run's, and every cell is compared with the file's profile of the same cell when the two cell lists are equal, with the
+file's pooled profile otherwise (mean shift, std ratio, Jensen-Shannon divergence, novel share, clip shares, jitter ratio).
+`<out>/eval/<preset>_observations.json` (itself a profile: the pooled one at its top level, one per cell under "profiles") and the
+figure `<preset>_observations.png` are written and the table, with the ten highest-ranked channels per cell below it, is printed and
+appended to `<preset>_observations.md`.
 Run on the GPU box."""
 import argparse
 import functools
@@ -237,6 +250,9 @@ MODES = (
     Mode("--sensitivity", "sensitivity", "run_sensitivity_sweep", "sensitivity_to_json", "sensitivity_markdown_table", "plot_sensitivity", "_sensitivity",
          "_sensitivity.png", "vx {a.vx}, robustness against the randomised dynamics", options=dict(parameters=None, pair=None, min_exposure=200),
          check=_check_sensitivity),
+    Mode("--observations", "observations", "run_observation_sweep", "observation_to_json", "observation_markdown_table", "plot_observations", "_observations",
+         "_observations.png", "vx {a.vx}, the distribution of the policy's observations", options=dict(against=None, no_privileged=False),
+         check=lambda a: a.against is not None and not os.path.isfile(a.against) and f"--against {a.against}: no such file"),
 )
 MODE = {mode.dest: mode for mode in MODES}
 
@@ -294,6 +310,9 @@ def parse_args(argv=None):
     ap.add_argument("--parameters", nargs="+", default=None, metavar="NAME", help="with --sensitivity: the parameters reported, default: those the preset randomises")
     ap.add_argument("--pair", nargs=2, default=None, metavar=("A", "B"), help="with --sensitivity: two parameters for the 8 x 8 hazard map")
     ap.add_argument("--min-exposure", type=int, default=None, help="with --sensitivity: steps a bin needs before it enters an effect, default 200 (a placeholder)")
+    ap.add_argument("--observations", action="store_true", help="measure the distribution of every observation column over the velocity grid, beside the scalar table")
+    ap.add_argument("--against", default=None, metavar="FILE.json", help="with --observations: an earlier run's JSON or a profile_from_array's to compare with; its edges become the ranges")
+    ap.add_argument("--no-privileged", action="store_const", const=True, default=None, help="with --observations: leave the privileged columns out")
     ap.add_argument("--out", required=True)
     a = ap.parse_args(argv)
     a.tiles = a.terrain == "tiles"
@@ -439,6 +458,7 @@ run_spectrum = functools.partial(run_mode, MODE["spectrum"])
 run_placement = functools.partial(run_mode, MODE["placement"])              # (its grid is the --axis product)
 run_episodes = functools.partial(run_mode, MODE["episodes"])
 run_sensitivity = functools.partial(run_mode, MODE["sensitivity"])
+run_observations = functools.partial(run_mode, MODE["observations"])
 
 
 def behaviour_axes(a):

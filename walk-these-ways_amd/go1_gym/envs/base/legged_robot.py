@@ -159,14 +159,20 @@ class LeggedRobot(BaseTask):
     # are (tests/test_family_wiring.py, tests/test_episode_metrics.py), so further rows go here: launched after the later families', in
     # this order, and named by load_state() after them and before the camera.
     _MORE_FAMILIES = (("sensitivity", "_sens", "go1sens_host", "Go1Sensitivity", "accumulate"),)
+    # The families after the sensitivity family, in the same five columns: the three tables above and the tuples made of them are pinned as
+    # they are (tests/test_family_wiring.py, tests/test_episode_metrics.py, tests/test_sensitivity_metrics.py), so further rows go here:
+    # launched after the sensitivity family's, in this order, and named by load_state() after it and before the camera.
+    _FURTHER_FAMILIES = (("observations", "_obs", "go1obs_host", "Go1Observations", "accumulate"),)
     _STEPPED = tuple((attr, method) for _, attr, _, _, method in _FAMILIES if method)
     _STEPPED_LATER = tuple((attr, method) for _, attr, _, _, method in _LATER_FAMILIES if method)
     _STEPPED_MORE = tuple((attr, method) for _, attr, _, _, method in _MORE_FAMILIES if method)
+    _STEPPED_FURTHER = tuple((attr, method) for _, attr, _, _, method in _FURTHER_FAMILIES if method)
     # load_state() is refused while one of them is armed: their accumulators are not part of a saved state
     _STATE_FAMILIES = tuple((name, attr) for name, attr, _, _, _ in _FAMILIES)
     _LATER_STATE_FAMILIES = tuple((name, attr) for name, attr, _, _, _ in _LATER_FAMILIES)
     _MORE_STATE_FAMILIES = tuple((name, attr) for name, attr, _, _, _ in _MORE_FAMILIES)
-    _HOST = {attr: (module, cls) for _, attr, module, cls, _ in _FAMILIES + _LATER_FAMILIES + _MORE_FAMILIES}
+    _FURTHER_STATE_FAMILIES = tuple((name, attr) for name, attr, _, _, _ in _FURTHER_FAMILIES)
+    _HOST = {attr: (module, cls) for _, attr, module, cls, _ in _FAMILIES + _LATER_FAMILIES + _MORE_FAMILIES + _FURTHER_FAMILIES}
     _HOST["_push"] = ("go1eval_host", "Go1Push")          # made by the first push_robots(); neither stepped nor a state family
 
     def __init__(self, cfg, sim_params, physics_engine, sim_device, headless, eval_cfg=None,
@@ -180,7 +186,7 @@ class LeggedRobot(BaseTask):
         self.initial_dynamics_dict = initial_dynamics_dict
         self._render = None               # go1render_host.Go1Render, created by the first start_recording() / render()
         self._frames = [[], []]           # per camera: the last complete recording handed out
-        for attr in self._HOST:           # _metrics ... _reward, _episodes, _sens and _push: each made by the first start_*() / push_robots() of its family
+        for attr in self._HOST:           # _metrics ... _reward, _episodes, _sens, _obs and _push: each made by the first start_*() / push_robots() of its family
             setattr(self, attr, None)
         self._state = None                # go1state_host.Go1State, created by the first save_state() / load_state()
         if eval_cfg is not None:          # reference legged_robot.py:41-42
@@ -481,7 +487,7 @@ class LeggedRobot(BaseTask):
                     self._behaviour.accumulate()
         if self._reward is not None and self._reward.armed:
             self._reward.accumulate(H.gravity_at(self.sim_config, self.common_step_counter))     # (the gravity of the step just taken)
-        for attr, method in self._STEPPED_LATER + self._STEPPED_MORE:
+        for attr, method in self._STEPPED_LATER + self._STEPPED_MORE + self._STEPPED_FURTHER:
             family = getattr(self, attr)
             if family is not None and family.armed:
                 getattr(family, method)()
@@ -524,6 +530,8 @@ class LeggedRobot(BaseTask):
             self._reward.snapshot()
         if self._sens is not None and self._sens.armed:             # the reset re-drew the motor parameters: what is in force from now
             self._sens.snapshot()
+        if self._obs is not None and self._obs.armed:               # the robots were put elsewhere between two steps: their next step folds no change
+            self._obs.note_reset(None if full else env_ids)
 
     def set_idx_pose(self, env_ids, dof_pos, base_state):
         """reference legged_robot.py:241-261: the buffers ARE the simulator state, so writing them is the push."""
@@ -958,6 +966,39 @@ class LeggedRobot(BaseTask):
         (groups, 4, 8, 8) or None, and the per-environment state}: one reduction launch and the device-to-host copies"""
         return self._started("read_sensitivity_metrics", "_sens", "start_sensitivity_metrics").read()
 
+    # ---- what the policy is fed (include/go1obs.h, libgo1obs.so: a library of its own): every column of obs_buf, and of
+    # privileged_obs_buf when asked, is a channel with its moments, sixteen bins and two tails over a range, the steps at the observation
+    # clip, and the moments of its change from one step to the next (the previous value is carried on the device: a reset step already
+    # holds the respawned robot's observation and folds no change).  One more launch per step while it is armed, after the sensitivity
+    # family's; independent of the other measurements.
+    def start_observation_metrics(self, groups, warmup_steps=0, ranges=None, privileged=True):
+        """begin an observation measurement: `groups` = one int per environment (the row of the result tables it counts towards, -1 =
+        not evaluated); the first warmup_steps steps after the start (or after a reset_idx from outside) enter nothing.  Every channel
+        gets sixteen bins over eval_metrics.observations.default_ranges(cfg) (placeholders by kind); ranges = {channel name or kind:
+        (lo, hi)} replaces them (observations.ranges_from(an earlier read) builds such a dict).  privileged=False leaves the privileged
+        columns out.  Refused if the names the configuration's switches give are not num_obs"""
+        self._need_gpu_metrics("start_observation_metrics")
+        from go1_gym_learn.eval_metrics import observations
+        names, kinds = observations.channel_names(self.cfg, privileged), observations.channel_kinds(self.cfg, privileged)
+        named = len(observations.channel_names(self.cfg))
+        if named != self.num_obs:
+            raise ValueError(f"start_observation_metrics(): the configuration's switches name {named} observation columns, the simulator has {self.num_obs}")
+        spans = observations.channel_spans(self.cfg, names, kinds, ranges)
+        family = self._family("start_observation_metrics", "_obs")
+        family.names, family.kinds = names, kinds
+        family.arm(groups, warmup_steps, spans=spans, privileged=privileged)
+
+    def stop_observation_metrics(self):
+        """stop folding steps; what was measured stays readable"""
+        self._disarm("stop_observation_metrics", "_obs")
+
+    def read_observation_metrics(self):
+        """go1obs_host.Go1Observations.read() with the channels' names: {"channels", "kinds", "edges": (C, 17), "clip", "value", "delta":
+        (groups, C, 6), "hist": (groups, C, 16), "tails": (groups, C, 3) below, above, at_clip, "groups": (groups, 4) environments,
+        launches, measured env-steps, resets (reset steps and resets from outside), and the per-environment state}: one reduction launch and the device-to-host copies"""
+        family = self._started("read_observation_metrics", "_obs", "start_observation_metrics")
+        return dict(family.read(), channels=list(family.names), kinds=list(family.kinds))
+
     def last_reward_terms(self):
         """((K + 4, N) scaled terms, sum, positive, negative and total of the last accumulated step, (N,) valid): views, no copy"""
         return self._started("last_reward_terms", "_reward", "start_reward_metrics").last()
@@ -999,7 +1040,7 @@ class LeggedRobot(BaseTask):
         branched environment's draws after the load are those of its own index.  Refused while a measurement family, a trace or a
         camera is armed: their accumulators are not part of the state, and a restore is a teleport to them."""
         stater = self._stater("load_state")
-        armed = [name for name, attr in self._STATE_FAMILIES + self._LATER_STATE_FAMILIES + self._MORE_STATE_FAMILIES if getattr(self, attr) is not None and getattr(self, attr).armed]
+        armed = [name for name, attr in self._STATE_FAMILIES + self._LATER_STATE_FAMILIES + self._MORE_STATE_FAMILIES + self._FURTHER_STATE_FAMILIES if getattr(self, attr) is not None and getattr(self, attr).armed]
         if self._render is not None and self._render.any_armed:
             armed.append("camera")
         if armed:

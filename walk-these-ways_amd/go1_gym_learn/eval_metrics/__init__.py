@@ -14,4 +14,6 @@ point and the Raibert heuristic's target, and the stride length and track width 
 curve with the episodes still open as censored observations (`run_episode_sweep`, `kaplan_meier`, `episode_to_json`,
 `episode_markdown_table`, `plot_survival`; include/go1episode.h), `sensitivity` how a policy holds up as the randomised dynamics move:
 exposure, falls, tracking errors and power per bin of friction, restitution, payload, centre-of-mass displacement and motor strength
-(`run_sensitivity_sweep`, `hazard`, `wilson`, `effect`, `rank_parameters`, `plot_sensitivity`; include/go1sens.h)."""
+(`run_sensitivity_sweep`, `hazard`, `wilson`, `effect`, `rank_parameters`, `plot_sensitivity`; include/go1sens.h), `observations` what the
+policy is fed: moments, histogram, tails, clip share and step-to-step change of every observation column, and how two such profiles differ
+(`run_observation_sweep`, `channel_names`, `profile`, `profile_from_array`, `shift`, `rank_channels`, `plot_observations`; include/go1obs.h)."""
