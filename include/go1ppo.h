@@ -156,7 +156,7 @@ int go1ppo_store_step(const float* rewards, const uint8_t* dones, const uint8_t*
                       float* env_bins_out, void* stream);
 
 /* GAE(lambda) backward scan over [T][N] buffers; returns and un-normalised advantages (= returns - values);
- * stats[0] += sum(adv), stats[1] += sum(adv^2) in double. */
+ * stats[0] += sum(adv), stats[1] += sum(adv^2) in double.  Returns -1 for N above 4096 * 256 (one workgroup per 256 environments). */
 int go1ppo_gae(const float* rewards, const uint8_t* dones, const float* values, const float* last_values, int T, int64_t N,
                float gamma, float lam, float* returns, float* advantages, double* stats, void* stream);
 
@@ -173,7 +173,7 @@ int go1ppo_ring_snapshot(const float* hist, int64_t ld_hist, int64_t N, int H, i
 
 /* One rollout step: ring_dst (row s + H - 1 of the ring, or NULL when the snapshot already wrote it) <- bf16(obs);
  * X (N x Kp) <- augmented rows of the windows starting at ring_window (= row s), the newest entry taken from `obs`;
- * obs_store / priv_store (fp32, or NULL) <- copies of obs (N x no) and priv (N x npv). */
+ * obs_store / priv_store (fp32, or NULL) <- copies of obs (N x no) and priv (N x npv).  Returns -1 for npv above 256. */
 int go1ppo_ring_step(const float* obs, const float* priv, void* ring_dst, const void* ring_window, int64_t N, int H, int no,
                      int npv, int Kp, void* X, float* obs_store, float* priv_store, void* stream);
 
