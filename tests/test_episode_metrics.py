@@ -4,6 +4,7 @@ tests/episode_ref.py on hand-computed episodes, the Kaplan-Meier estimate agains
 product-limit estimate, go1episode.hip itself under the SIMT emulator against that model bit for bit (accumulators, state, histograms
 and both result tables), the environment hooks where there is no GPU, the tool's parsing and the order of the sweep's calls."""
 import ctypes
+import functools
 import inspect
 import json
 import os
@@ -443,7 +444,12 @@ def plane_env(monkeypatch, num_envs=16):
 
 def test_episode_hooks_on_cpu_buffers(monkeypatch):
     from go1_gym.envs.base.legged_robot import LeggedRobot
-    from test_family_wiring import STATE_FAMILIES, STEPPED, Stub, put_stubs
+    from test_family_wiring import FAMILIES, REWARD, STATE_FAMILIES, Stub
+    import test_family_wiring as wiring
+    # stubs for the families up to the reward family only: the later ones stay None unless this test puts its own stub there, so the
+    # launch-order and refusal checks below name exactly the families they set
+    STEPPED = wiring.STEPPED[:REWARD + 1]
+    put_stubs = functools.partial(wiring.put_stubs, stepped=STEPPED)
     env = plane_env(monkeypatch)
     env.step(torch.zeros(16, 12))
     for call in (lambda: env.start_episode_metrics(torch.zeros(16, dtype=torch.int32)), env.stop_episode_metrics, env.read_episode_metrics):
@@ -456,9 +462,11 @@ def test_episode_hooks_on_cpu_buffers(monkeypatch):
     assert list(signature.parameters) == ["groups", "warmup_steps", "gamma", "bin_steps"]
     for name in ("start_episode_metrics", "stop_episode_metrics", "read_episode_metrics"):
         assert (getattr(LeggedRobot, name).__doc__ or "").strip(), name
-    # the second table: the eleven pinned rows stay as they are, the new row follows them
-    assert env._STATE_FAMILIES == STATE_FAMILIES and env._LATER_STATE_FAMILIES == (("episodes", "_episodes"),) and env._STEPPED_LATER == (("_episodes", "accumulate"),)
-    assert env._HOST["_episodes"] == ("go1episode_host", "Go1Episodes") and all(len(row) == 5 for row in env._LATER_FAMILIES)
+    # its row of the one table, directly after the reward family's
+    k = [row[0] for row in env._FAMILIES].index("episodes")
+    assert env._FAMILIES == FAMILIES and env._FAMILIES[k] == ("episodes", "_episodes", "go1episode_host", "Go1Episodes", "accumulate") and env._FAMILIES[k - 1][0] == "rewards"
+    assert env._STATE_FAMILIES == STATE_FAMILIES and env._STATE_FAMILIES[k] == ("episodes", "_episodes") and env._STEPPED[k - 2:k] == (("_reward", "accumulate"), ("_episodes", "accumulate"))
+    assert env._HOST["_episodes"] == ("go1episode_host", "Go1Episodes") and all(len(row) == 5 for row in env._FAMILIES)
     # launched last, after the reward family's
     log = []
     put_stubs(env, log)

@@ -14,13 +14,31 @@ import pytest
 import torch
 
 REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-HOST_MODULES = ("go1eval_host", "go1feet_host", "go1trunk_host", "go1gait_host", "go1spectrum_host", "go1place_host", "go1reward_host", "go1state_host")
+HOST_MODULES = ("go1eval_host", "go1feet_host", "go1trunk_host", "go1gait_host", "go1spectrum_host", "go1place_host", "go1reward_host", "go1episode_host",
+                "go1sens_host", "go1obs_host", "go1state_host")
 # (attribute, per-step method) in launch order
 STEPPED = [("_metrics", "accumulate"), ("_behaviour", "accumulate"), ("_trace", "record"), ("_traversal", "accumulate"), ("_joints", "accumulate"),
            ("_feet", "accumulate"), ("_trunk", "accumulate"), ("_gait", "accumulate"), ("_spectrum", "accumulate"), ("_place", "accumulate"),
-           ("_reward", "accumulate")]
+           ("_reward", "accumulate"), ("_episodes", "accumulate"), ("_sens", "accumulate"), ("_obs", "accumulate")]
 STATE_FAMILIES = (("metrics", "_metrics"), ("behaviour", "_behaviour"), ("trace", "_trace"), ("terrain", "_traversal"), ("joints", "_joints"),
-                  ("feet", "_feet"), ("trunk", "_trunk"), ("gait", "_gait"), ("spectrum", "_spectrum"), ("placement", "_place"), ("rewards", "_reward"))
+                  ("feet", "_feet"), ("trunk", "_trunk"), ("gait", "_gait"), ("spectrum", "_spectrum"), ("placement", "_place"), ("rewards", "_reward"),
+                  ("episodes", "_episodes"), ("sensitivity", "_sens"), ("observations", "_obs"))
+# the whole table: name, attribute, host module, class, per-step method (the behaviour table has none: it is folded beside the scalar one)
+FAMILIES = (("metrics", "_metrics", "go1eval_host", "Go1Eval", "accumulate"),
+            ("behaviour", "_behaviour", "go1eval_host", "Go1Behaviour", None),
+            ("trace", "_trace", "go1eval_host", "Go1Trace", "record"),
+            ("terrain", "_traversal", "go1eval_host", "Go1Terrain", "accumulate"),
+            ("joints", "_joints", "go1eval_host", "Go1Joints", "accumulate"),
+            ("feet", "_feet", "go1feet_host", "Go1Feet", "accumulate"),
+            ("trunk", "_trunk", "go1trunk_host", "Go1Trunk", "accumulate"),
+            ("gait", "_gait", "go1gait_host", "Go1Gait", "accumulate"),
+            ("spectrum", "_spectrum", "go1spectrum_host", "Go1Spectrum", "accumulate"),
+            ("placement", "_place", "go1place_host", "Go1Place", "accumulate"),
+            ("rewards", "_reward", "go1reward_host", "Go1Reward", "accumulate"),
+            ("episodes", "_episodes", "go1episode_host", "Go1Episodes", "accumulate"),
+            ("sensitivity", "_sens", "go1sens_host", "Go1Sensitivity", "accumulate"),
+            ("observations", "_obs", "go1obs_host", "Go1Observations", "accumulate"))
+REWARD = STEPPED.index(("_reward", "accumulate"))
 
 
 def plane_env(monkeypatch, num_envs=16):
@@ -49,9 +67,15 @@ class Stub:
     def record(self, *args):
         self.log.append((self.attr, "record", args))
 
+    def snapshot(self, *args):                                                # (reset_idx tells the sensitivity family; not a per-step call)
+        pass
 
-def put_stubs(env, log, armed=True):
-    for attr, _ in STEPPED:
+    def note_reset(self, *args):                                              # (reset_idx tells the observation family; not a per-step call)
+        pass
+
+
+def put_stubs(env, log, armed=True, stepped=STEPPED):
+    for attr, _ in stepped:
         setattr(env, attr, Stub(attr, log, armed))
 
 
@@ -68,8 +92,8 @@ def test_step_calls_the_armed_families_in_launch_order(monkeypatch):
     env.step(zero)
     assert env.common_step_counter == counter + 1
     assert [(attr, method) for attr, method, _ in log] == STEPPED
-    assert all(args == () for _, _, args in log[:-1])
-    (gravity,) = log[-1][2]                                                   # the gravity of the step just taken: the counter before its increment
+    assert all(args == () for k, (_, _, args) in enumerate(log) if k != REWARD)      # the reward stub alone receives an argument
+    (gravity,) = log[REWARD][2]                                               # the gravity of the step just taken: the counter before its increment
     assert np.array_equal(gravity, H.gravity_at(env.sim_config, counter)) and gravity.shape == (3,)
     # the behaviour table is folded only beside the scalar one
     del log[:]
@@ -99,14 +123,21 @@ def test_step_calls_the_armed_families_in_launch_order(monkeypatch):
 
 # ---- 2. the state families -----------------------------------------------------------------------------------------------------------------------
 def test_state_families_and_the_refusal_of_load_state(monkeypatch):
+    from go1_gym.envs.base.legged_robot import LeggedRobot
     env = plane_env(monkeypatch)
     assert env._STATE_FAMILIES == STATE_FAMILIES and isinstance(env._STATE_FAMILIES, tuple)
+    # the one table, whole: fourteen rows of five columns, and everything else made of it
+    assert LeggedRobot._FAMILIES == FAMILIES and len(FAMILIES) == 14 and all(len(row) == 5 for row in LeggedRobot._FAMILIES)
+    assert LeggedRobot._STEPPED == tuple(pair for pair in STEPPED if pair[0] != "_behaviour")
+    assert list(LeggedRobot._HOST) == [row[1] for row in FAMILIES] + ["_push"] and len(LeggedRobot._HOST) == 15 and list(LeggedRobot._HOST)[-2:] == ["_obs", "_push"]
+    assert all(LeggedRobot._HOST[attr] == (module, cls) for _, attr, module, cls, _ in FAMILIES) and LeggedRobot._HOST["_push"] == ("go1eval_host", "Go1Push")
+    assert not [name for name in dir(LeggedRobot) if "LATER" in name or "MORE_" in name or "FURTHER" in name]      # no table beside the table
     restored = []
     env._state = types.SimpleNamespace(restore=lambda *a, **k: restored.append((a, k)))       # the state library is never reached by a refusal
     put_stubs(env, [])
     with pytest.raises(RuntimeError) as e:
         env.load_state(None)
-    assert "load_state(): refused while metrics, behaviour, trace, terrain, joints, feet, trunk, gait, spectrum, placement, rewards are armed: stop them first" in str(e.value)
+    assert "load_state(): refused while metrics, behaviour, trace, terrain, joints, feet, trunk, gait, spectrum, placement, rewards, episodes, sensitivity, observations are armed: stop them first" in str(e.value)
     put_stubs(env, [], armed=False)
     env._place.armed = True
     with pytest.raises(RuntimeError, match=r"refused while placement is armed: stop it first"):

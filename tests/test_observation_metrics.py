@@ -5,6 +5,7 @@ tables), the environment hooks where there is no GPU, the channel names against 
 simulator, against the buffers they are named after, shift and ranking by hand, profile_from_array against the model, the sweep's files
 and the tool's parsing."""
 import ctypes
+import functools
 import inspect
 import json
 import os
@@ -403,7 +404,12 @@ def plane_env(monkeypatch, num_envs=16, noise=True):
 
 def test_observation_hooks_on_cpu_buffers(monkeypatch):
     from go1_gym.envs.base.legged_robot import LeggedRobot
-    from test_family_wiring import STATE_FAMILIES, STEPPED, Stub, put_stubs
+    from test_family_wiring import FAMILIES, REWARD, STATE_FAMILIES, Stub
+    import test_family_wiring as wiring
+    # stubs for the families up to the reward family only: the later ones stay None unless this test puts its own stub there, so the
+    # launch-order and refusal checks below name exactly the families they set
+    STEPPED = wiring.STEPPED[:REWARD + 1]
+    put_stubs = functools.partial(wiring.put_stubs, stepped=STEPPED)
     env = plane_env(monkeypatch)
     env.step(torch.zeros(16, 12))
     for call in (lambda: env.start_observation_metrics(torch.zeros(16, dtype=torch.int32)), env.stop_observation_metrics, env.read_observation_metrics):
@@ -416,10 +422,11 @@ def test_observation_hooks_on_cpu_buffers(monkeypatch):
     assert list(signature.parameters) == ["groups", "warmup_steps", "ranges", "privileged"]
     for name in ("start_observation_metrics", "stop_observation_metrics", "read_observation_metrics"):
         assert (getattr(LeggedRobot, name).__doc__ or "").strip(), name
-    # a fourth table: the pinned rows of the first three stay as they are, the new row follows them
-    assert env._STATE_FAMILIES == STATE_FAMILIES and env._LATER_STATE_FAMILIES == (("episodes", "_episodes"),) and env._MORE_STATE_FAMILIES == (("sensitivity", "_sens"),)
-    assert env._FURTHER_FAMILIES == (("observations", "_obs", "go1obs_host", "Go1Observations", "accumulate"),)
-    assert env._FURTHER_STATE_FAMILIES == (("observations", "_obs"),) and env._STEPPED_FURTHER == (("_obs", "accumulate"),) and env._HOST["_obs"] == ("go1obs_host", "Go1Observations")
+    # its row of the one table, directly after the sensitivity family's
+    k = [row[0] for row in env._FAMILIES].index("observations")
+    assert env._FAMILIES == FAMILIES and env._FAMILIES[k] == ("observations", "_obs", "go1obs_host", "Go1Observations", "accumulate") and env._FAMILIES[k - 1][0] == "sensitivity"
+    assert env._STATE_FAMILIES == STATE_FAMILIES and env._STATE_FAMILIES[k] == ("observations", "_obs") and env._STEPPED[k - 2:k] == (("_sens", "accumulate"), ("_obs", "accumulate"))
+    assert env._HOST["_obs"] == ("go1obs_host", "Go1Observations") and all(len(row) == 5 for row in env._FAMILIES) and env._FAMILIES[-1][0] == "observations"
     assert list(env._HOST)[-2:] == ["_obs", "_push"] and len(env._HOST) == 15
     # launched last, after the sensitivity family's
     log = []

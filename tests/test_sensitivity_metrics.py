@@ -5,6 +5,7 @@ that model bit for bit (accumulators, state and the four result tables), the env
 the tool's parsing, the sweep's files, and the GPU environment test's rollout on the oracle-backed simulator with the emulated kernels
 stepped by the environment itself."""
 import ctypes
+import functools
 import inspect
 import json
 import os
@@ -555,7 +556,12 @@ def plane_env(monkeypatch, num_envs=16):
 
 def test_sensitivity_hooks_on_cpu_buffers(monkeypatch):
     from go1_gym.envs.base.legged_robot import LeggedRobot
-    from test_family_wiring import STATE_FAMILIES, STEPPED, Stub, put_stubs
+    from test_family_wiring import FAMILIES, REWARD, STATE_FAMILIES, Stub
+    import test_family_wiring as wiring
+    # stubs for the families up to the reward family only: the later ones stay None unless this test puts its own stub there, so the
+    # launch-order and refusal checks below name exactly the families they set
+    STEPPED = wiring.STEPPED[:REWARD + 1]
+    put_stubs = functools.partial(wiring.put_stubs, stepped=STEPPED)
     env = plane_env(monkeypatch)
     env.step(torch.zeros(16, 12))
     for call in (lambda: env.start_sensitivity_metrics(torch.zeros(16, dtype=torch.int32)), env.stop_sensitivity_metrics, env.read_sensitivity_metrics):
@@ -568,10 +574,11 @@ def test_sensitivity_hooks_on_cpu_buffers(monkeypatch):
     assert list(signature.parameters) == ["groups", "warmup_steps", "ranges", "pair"]
     for name in ("start_sensitivity_metrics", "stop_sensitivity_metrics", "read_sensitivity_metrics"):
         assert (getattr(LeggedRobot, name).__doc__ or "").strip(), name
-    # a third table: the pinned rows of the first two stay as they are, the new row follows them
-    assert env._STATE_FAMILIES == STATE_FAMILIES and env._LATER_STATE_FAMILIES == (("episodes", "_episodes"),) and env._STEPPED_LATER == (("_episodes", "accumulate"),)
-    assert env._MORE_FAMILIES == (("sensitivity", "_sens", "go1sens_host", "Go1Sensitivity", "accumulate"),)
-    assert env._MORE_STATE_FAMILIES == (("sensitivity", "_sens"),) and env._STEPPED_MORE == (("_sens", "accumulate"),) and env._HOST["_sens"] == ("go1sens_host", "Go1Sensitivity")
+    # its row of the one table, directly after the episode family's
+    k = [row[0] for row in env._FAMILIES].index("sensitivity")
+    assert env._FAMILIES == FAMILIES and env._FAMILIES[k] == ("sensitivity", "_sens", "go1sens_host", "Go1Sensitivity", "accumulate") and env._FAMILIES[k - 1][0] == "episodes"
+    assert env._STATE_FAMILIES == STATE_FAMILIES and env._STATE_FAMILIES[k] == ("sensitivity", "_sens") and env._STEPPED[k - 2:k] == (("_episodes", "accumulate"), ("_sens", "accumulate"))
+    assert env._HOST["_sens"] == ("go1sens_host", "Go1Sensitivity") and all(len(row) == 5 for row in env._FAMILIES)
     # launched last, after the episode family's
     log = []
 

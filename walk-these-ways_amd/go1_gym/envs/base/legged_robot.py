@@ -138,8 +138,8 @@ class _SimFaults(_LazyMapping):
 class LeggedRobot(BaseTask):
     # The measurement families, one row each, in the order step() launches them: the name load_state() reports, the attribute the
     # family object is kept under, the host module and the class it is made of (the module is imported by the family's first start_*()),
-    # and the method step() calls while the family is armed.  Two rows have none: the behaviour table is folded inside the scalar
-    # table's branch only, and the reward family's accumulate() takes the gravity of the step just taken; step() spells both out.
+    # and the method step() calls while the family is armed.  The behaviour table has none: it is folded inside the scalar table's branch
+    # only.  The reward family's accumulate() takes the gravity of the step just taken.  step() spells both out.
     _FAMILIES = (("metrics", "_metrics", "go1eval_host", "Go1Eval", "accumulate"),
                  ("behaviour", "_behaviour", "go1eval_host", "Go1Behaviour", None),
                  ("trace", "_trace", "go1eval_host", "Go1Trace", "record"),
@@ -150,29 +150,14 @@ class LeggedRobot(BaseTask):
                  ("gait", "_gait", "go1gait_host", "Go1Gait", "accumulate"),
                  ("spectrum", "_spectrum", "go1spectrum_host", "Go1Spectrum", "accumulate"),
                  ("placement", "_place", "go1place_host", "Go1Place", "accumulate"),
-                 ("rewards", "_reward", "go1reward_host", "Go1Reward", None))
-    # The families that came after those eleven, in the same five columns.  They are a table of their own because the eleven rows above, the
-    # stepped order and _STATE_FAMILIES made of them are pinned as they are (tests/test_family_wiring.py): a row here is launched after
-    # the reward family's, in this order, and load_state() names it after the eleven and before the camera.
-    _LATER_FAMILIES = (("episodes", "_episodes", "go1episode_host", "Go1Episodes", "accumulate"),)
-    # The families after the episode family, in the same five columns: the two tables above and the tuples made of them are pinned as they
-    # are (tests/test_family_wiring.py, tests/test_episode_metrics.py), so further rows go here: launched after the later families', in
-    # this order, and named by load_state() after them and before the camera.
-    _MORE_FAMILIES = (("sensitivity", "_sens", "go1sens_host", "Go1Sensitivity", "accumulate"),)
-    # The families after the sensitivity family, in the same five columns: the three tables above and the tuples made of them are pinned as
-    # they are (tests/test_family_wiring.py, tests/test_episode_metrics.py, tests/test_sensitivity_metrics.py), so further rows go here:
-    # launched after the sensitivity family's, in this order, and named by load_state() after it and before the camera.
-    _FURTHER_FAMILIES = (("observations", "_obs", "go1obs_host", "Go1Observations", "accumulate"),)
+                 ("rewards", "_reward", "go1reward_host", "Go1Reward", "accumulate"),
+                 ("episodes", "_episodes", "go1episode_host", "Go1Episodes", "accumulate"),
+                 ("sensitivity", "_sens", "go1sens_host", "Go1Sensitivity", "accumulate"),
+                 ("observations", "_obs", "go1obs_host", "Go1Observations", "accumulate"))
     _STEPPED = tuple((attr, method) for _, attr, _, _, method in _FAMILIES if method)
-    _STEPPED_LATER = tuple((attr, method) for _, attr, _, _, method in _LATER_FAMILIES if method)
-    _STEPPED_MORE = tuple((attr, method) for _, attr, _, _, method in _MORE_FAMILIES if method)
-    _STEPPED_FURTHER = tuple((attr, method) for _, attr, _, _, method in _FURTHER_FAMILIES if method)
     # load_state() is refused while one of them is armed: their accumulators are not part of a saved state
     _STATE_FAMILIES = tuple((name, attr) for name, attr, _, _, _ in _FAMILIES)
-    _LATER_STATE_FAMILIES = tuple((name, attr) for name, attr, _, _, _ in _LATER_FAMILIES)
-    _MORE_STATE_FAMILIES = tuple((name, attr) for name, attr, _, _, _ in _MORE_FAMILIES)
-    _FURTHER_STATE_FAMILIES = tuple((name, attr) for name, attr, _, _, _ in _FURTHER_FAMILIES)
-    _HOST = {attr: (module, cls) for _, attr, module, cls, _ in _FAMILIES + _LATER_FAMILIES + _MORE_FAMILIES + _FURTHER_FAMILIES}
+    _HOST = {attr: (module, cls) for _, attr, module, cls, _ in _FAMILIES}
     _HOST["_push"] = ("go1eval_host", "Go1Push")          # made by the first push_robots(); neither stepped nor a state family
 
     def __init__(self, cfg, sim_params, physics_engine, sim_device, headless, eval_cfg=None,
@@ -186,7 +171,7 @@ class LeggedRobot(BaseTask):
         self.initial_dynamics_dict = initial_dynamics_dict
         self._render = None               # go1render_host.Go1Render, created by the first start_recording() / render()
         self._frames = [[], []]           # per camera: the last complete recording handed out
-        for attr in self._HOST:           # _metrics ... _reward, _episodes, _sens, _obs and _push: each made by the first start_*() / push_robots() of its family
+        for attr in self._HOST:           # _metrics ... _obs and _push: each made by the first start_*() / push_robots() of its family
             setattr(self, attr, None)
         self._state = None                # go1state_host.Go1State, created by the first save_state() / load_state()
         if eval_cfg is not None:          # reference legged_robot.py:41-42
@@ -482,15 +467,12 @@ class LeggedRobot(BaseTask):
         for attr, method in self._STEPPED:
             family = getattr(self, attr)
             if family is not None and family.armed:
-                getattr(family, method)()
+                if attr == "_reward":
+                    family.accumulate(H.gravity_at(self.sim_config, self.common_step_counter))     # (the gravity of the step just taken)
+                else:
+                    getattr(family, method)()
                 if attr == "_metrics" and self._behaviour is not None and self._behaviour.armed:      # (only beside the scalar table)
                     self._behaviour.accumulate()
-        if self._reward is not None and self._reward.armed:
-            self._reward.accumulate(H.gravity_at(self.sim_config, self.common_step_counter))     # (the gravity of the step just taken)
-        for attr, method in self._STEPPED_LATER + self._STEPPED_MORE + self._STEPPED_FURTHER:
-            family = getattr(self, attr)
-            if family is not None and family.armed:
-                getattr(family, method)()
         if self._curriculum_sync and (self.common_step_counter + 1) % self.sim_config.curriculum_update_interval == 0:
             # ONE exchange for the last `curriculum_update_interval` steps' success counts (a slot per step), then the per-step
             # updates in order: every rank applies what a single process over the concatenated shards would
@@ -1040,7 +1022,7 @@ class LeggedRobot(BaseTask):
         branched environment's draws after the load are those of its own index.  Refused while a measurement family, a trace or a
         camera is armed: their accumulators are not part of the state, and a restore is a teleport to them."""
         stater = self._stater("load_state")
-        armed = [name for name, attr in self._STATE_FAMILIES + self._LATER_STATE_FAMILIES + self._MORE_STATE_FAMILIES + self._FURTHER_STATE_FAMILIES if getattr(self, attr) is not None and getattr(self, attr).armed]
+        armed = [name for name, attr in self._STATE_FAMILIES if getattr(self, attr) is not None and getattr(self, attr).armed]
         if self._render is not None and self._render.any_armed:
             armed.append("camera")
         if armed:
