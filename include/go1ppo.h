@@ -113,6 +113,15 @@ typedef struct {
   int32_t num_nets, _pad;
   Go1PpoTailNet net[GO1PPO_TAIL_MAX_NETS];
 } Go1PpoTailArgs;
+/* One launch: 32 rows per workgroup, ceil(max rows / 32) x num_nets workgroups; the nets may differ in rows and depth.
+ * Returns, before any launch,
+ *  -1: args NULL; num_nets outside 1 .. GO1PPO_TAIL_MAX_NETS; for any net a NULL or not 16-byte aligned `in`, rows <= 0, num_layers
+ *      outside 1 .. GO1PPO_TAIL_MAX_LAYERS, or ld_in not a multiple of 8;
+ *  -2 (checked after the -1 conditions of every net): a layer with a NULL W or bias, k_in outside 32 .. 512 or not a multiple of 32,
+ *      n_out outside 16 .. 512 or not a multiple of 16, W not 16-byte aligned, k_in != the previous layer's n_out, or ld_out < n_out
+ *      with a non-NULL out; ld_in < layer[0].k_in; elu_in != 0 with a non-NULL latent and a NULL wz, npv < 1, lat_ld < npv or
+ *      wz_ld < npv (npv, wz, lat_ld and wz_ld are not looked at without elu_in or with a NULL latent);
+ *  -9: the launch itself failed. */
 int go1ppo_tail_fwd(const Go1PpoTailArgs* args, void* stream);
 
 /* One weight-gradient problem of a batched launch (same contract as go1ppo_wgrad).  The caller fills the first ten

@@ -1439,16 +1439,22 @@ extern "C" int go1ppo_opt_partials(void) { return OPT_BLOCKS; }
 extern "C" int go1ppo_tail_fwd(const Go1PpoTailArgs* args, void* stream) {
   if (!args || args->num_nets <= 0 || args->num_nets > GO1PPO_TAIL_MAX_NETS) return -1;
   int64_t max_rows = 0;
-  for (int i = 0; i < args->num_nets; i++) {
+  for (int i = 0; i < args->num_nets; i++) {                    // -1 over the whole table first
     const Go1PpoTailNet& N = args->net[i];
     if (!N.in || N.rows <= 0 || N.num_layers <= 0 || N.num_layers > GO1PPO_TAIL_MAX_LAYERS || (N.ld_in & 7) || !aligned16(N.in)) return -1;
+    if (N.rows > max_rows) max_rows = N.rows;
+  }
+  for (int i = 0; i < args->num_nets; i++) {
+    const Go1PpoTailNet& N = args->net[i];
     for (int l = 0; l < N.num_layers; l++) {
       const Go1PpoTailLayer& L = N.layer[l];
       if (!L.W || !L.bias || L.k_in <= 0 || L.k_in > TF_MAXK || (L.k_in & 31) || L.n_out <= 0 || L.n_out > TF_MAXK || (L.n_out & 15) ||
           !aligned16(L.W) || (l > 0 && L.k_in != N.layer[l - 1].n_out) || (L.out && L.ld_out < L.n_out))
         return -2;
     }
-    if (N.rows > max_rows) max_rows = N.rows;
+    // what would send the staging loop out of its buffers: input rows narrower than the first layer, a latent term without its operands
+    if (N.ld_in < N.layer[0].k_in) return -2;
+    if (N.elu_in && N.latent && (!N.wz || N.npv < 1 || N.lat_ld < N.npv || N.wz_ld < N.npv)) return -2;
   }
   tail_fwd_kernel<32><<<dim3((unsigned)((max_rows + 31) / 32), args->num_nets), dim3(256), 0, (hipStream_t)stream>>>(*args);
   return hipGetLastError() == hipSuccess ? 0 : -9;
